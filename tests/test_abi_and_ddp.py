@@ -278,6 +278,36 @@ def test_bench_two_rank_train_path_end_to_end_on_cpu():
     assert d["allreduce_bytes_per_step"] > 4e6 and np.isfinite(d["loss"])
 
 
+def test_bench_dump_outputs_repeat_run_to_run(tmp_path):
+    """`bench.py --dump-outputs DIR` through the train path on the tests' CPU stand-ins of the kernels (--emu): DIR holds what the
+    last timed step computed (the loss the line reports, the gradient norm, seeded samples of the updated parameters and of the
+    step's gradients) in float32 / float64 within 64 MiB, and a second run with the same arguments writes the same arrays"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "4"
+    runs = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--emu", "--steps", "2", "--warmup", "1",
+                            "--batch", "2", "--seq", "16", "--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["warmup"] == 1
+        arrays = {f.stem: np.load(f) for f in (tmp_path / name).glob("*.npy")}
+        assert set(arrays) == {"loss", "grad_norm", "params_sample", "grads_sample"}
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        assert float(arrays["loss"][0]) == d["loss"]
+        runs.append(arrays)
+    for k in runs[0]:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k], err_msg=k)
+
+
 def test_bench_allreduce_summary_semantics():
     """bench.py's `allreduce_*` keys under --accumulate 2: the reducer reports one exchange per optimiser step (the whole flat
     gradient buffer, 467,685,376 B for tv2o-medium in bf16), i.e. one per TWO timed steps; per timed step that is half."""

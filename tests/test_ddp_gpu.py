@@ -183,7 +183,7 @@ def test_bench_multi_gpu_code_path_rehearsal_on_the_real_backend():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--comm", "both",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--baseline-1gpu", "300000"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--baseline-1gpu", "300000"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -206,16 +206,18 @@ def test_bench_multi_gpu_code_path_rehearsal_on_the_real_backend():
                                         ("block", ["--block-batch", "2", "--block-seq", "512", "--block-unfolded"]),
                                         ("generate", ["--gen-batch", "4", "--gen-events", "12"])],
                          ids=["block_folded", "block_unfolded", "generate"])
-def test_bench_modes_print_one_valid_line(mode, extra):
+def test_bench_modes_print_one_valid_line(mode, extra, tmp_path):
     """the other modes of bench.py (the `block` and `generate` objects of the driver's line come from the same functions) at toy
-    sizes: one JSON line on stdout with the contract's keys and a roofline object; the folded and unfolded block forms both run"""
+    sizes: one JSON line on stdout with the contract's keys and a roofline object; the folded and unfolded block forms both run;
+    --dump-outputs writes the last call's output (the block's [B*S, D] output, generate()'s (B, 1 + events, 8) ids)"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", mode, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", *extra],
-                       capture_output=True, text=True, env=env, timeout=600)
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", mode, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", *extra,
+                        "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-1000:]
@@ -227,3 +229,60 @@ def test_bench_modes_print_one_valid_line(mode, extra):
         assert d["block"]["norms_folded"] == ("--block-unfolded" not in extra)
         names = set(d["block"]["kernels"])
         assert ("mh_gemm_rowss" in names) == d["block"]["norms_folded"] and ("mh_rmsnorm_fwd" in names) != d["block"]["norms_folded"]
+    arrays = {f.stem: np.load(f) for f in out.glob("*.npy")}
+    if mode == "block":
+        assert set(arrays) == {"hidden_sample"} and arrays["hidden_sample"].shape == (2 * 512, 1024)
+    else:
+        assert set(arrays) == {"ids"} and arrays["ids"].shape == (4, 13, 8)
+        ids = arrays["ids"]
+        assert (ids == np.round(ids)).all() and ids.min() >= 0 and ids.max() < mm.MIDITokenizerV2().vocab_size and (ids[:, 1:, 0] > 0).all()
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full (at a toy batch): exactly K timed steps and the headline keys, none of
+    the --full measurements, and --dump-outputs writes what the last timed step computed -- the loss the line reports, the gradient
+    norm, seeded samples of the updated parameters and of the step's gradients -- as float32 / float64 within 64 MiB"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--seq", "256", "--dump-outputs", str(out)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1 and d["unit"] == "events/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and d["metric"].startswith("MIDI events/sec, training step")
+    assert abs(d["value"] - 2 * 256 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    for k in ("roofline", "kernel_families", "attention", "allreduce_contention", "block", "generate", "large", "large_2x_hidden",
+              "cpu_baseline"):
+        assert k not in d, k
+    arrays = {f.stem: np.load(f) for f in out.glob("*.npy")}
+    assert set(arrays) == {"loss", "grad_norm", "params_sample", "grads_sample"}
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert float(arrays["loss"][0]) == d["loss"] and arrays["grad_norm"][0] > 0
+    assert arrays["params_sample"].size == arrays["grads_sample"].size > 1 << 20
+    assert "value_no_gemm_events" not in d and "ms_per_step_no_gemm_events" not in d
+    # --full steps the model on after the timed region (the re-run without GEMM events, two kernel-family steps, the last of them on
+    # the other batch): its dump must still be the timed region's last step, i.e. what the plain run of the same arguments wrote
+    full = tmp_path / "outputs_full"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                        "--seq", "256", "--full", "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(full)],
+                       capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    df = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert "roofline" in df and "kernel_families" in df and df["value_no_gemm_events"] > 0
+    fa = {f.stem: np.load(f) for f in full.glob("*.npy")}
+    assert set(fa) == set(arrays) and float(fa["loss"][0]) == df["loss"]
+    # (the embedding backward adds with fp32 atomics: the last bits of the gradients, and rarely of the bf16 weights, may differ)
+    assert abs(fa["loss"][0] - arrays["loss"][0]) <= 1e-6 * abs(arrays["loss"][0]), (fa["loss"], arrays["loss"])
+    assert abs(fa["grad_norm"][0] - arrays["grad_norm"][0]) <= 1e-4 * arrays["grad_norm"][0], (fa["grad_norm"], arrays["grad_norm"])
+    g_full, g = fa["grads_sample"].astype(np.float64), arrays["grads_sample"].astype(np.float64)
+    assert np.linalg.norm(g_full - g) <= 1e-3 * np.linalg.norm(g), np.linalg.norm(g_full - g) / np.linalg.norm(g)
+    changed = float(np.mean(fa["params_sample"] != arrays["params_sample"]))
+    assert changed <= 1e-4, changed

@@ -1,5 +1,5 @@
 #!/bin/bash
-# One profile run for profiles/: GPU suite, default bench line (CPU baseline included), rocprofv3 kernel stats of the same
+# One profile run for profiles/: GPU suite, the --full bench line (CPU baseline included), rocprofv3 kernel stats of the same
 # command, PMC traffic passes, attention forms A/B.  Usage: tools/gpu_profile_run.sh <tag>   (outputs gpurun_out/<tag>_*)
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
@@ -11,7 +11,7 @@ timeout 2400 python -m pytest tests/ -q -m gpu --tb=short -p no:cacheprovider > 
 echo "gpu tests rc=$?" >> $O/${T}_gpu_tests.log
 tail -n 3 $O/${T}_gpu_tests.log
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $O/${T}_smoke.log 2>&1; echo "smoke rc=$?" >> $O/${T}_smoke.log; tail -n 2 $O/${T}_smoke.log
-timeout 1200 python bench.py > $O/${T}_bench.json 2> $O/${T}_gemm_by_shape.txt
+timeout 1200 python bench.py --full > $O/${T}_bench.json 2> $O/${T}_gemm_by_shape.txt
 echo "bench rc=$?"
 (cd /tmp && rm -rf /tmp/prof_$T && timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$T -o bench -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $O/${T}_rocprof_bench.log 2>&1)
 cp $(find /tmp/prof_$T -name "*kernel_stats.csv" | head -1) $O/${T}_rocprofv3_kernel_stats.csv 2>/dev/null
