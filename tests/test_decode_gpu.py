@@ -174,13 +174,25 @@ def test_chunked_continuation_of_a_cached_forward(orc, tok, golden, dtype):
     a 300-event prefill, a 212-event chunk (its first query tile starts below the cached length: 300 is not a multiple of 128), a
     129-event chunk, then one event -- against the oracle's cached forward fed the same chunks, and against the uncached forward
     over all 642 events.  fp32: rtol 1e-3 on every hidden state; bf16: within 1.5x the reference's own bf16 drift."""
+    _chunked_continuation(orc, tok, golden, dtype, (0, 300, 512, 641, 642))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_chunked_continuation_from_tile_boundaries(orc, tok, golden, dtype):
+    """test_chunked_continuation_of_a_cached_forward with chunks starting on a 128-row tile boundary (256) and on a 64-row
+    boundary that is not a 128-row one (320: the bf16 tail computes the whole 128-row tile from 256, fp32 its 64-row tiles
+    from 320), then 129 events and one; same bounds"""
+    _chunked_continuation(orc, tok, golden, dtype, (0, 256, 320, 449, 450))
+
+
+def _chunked_continuation(orc, tok, golden, dtype, cuts):
     from midi_model_amd.engine import KVState
     shp = orc.Shape(vocab=tok.vocab_size)
     sd = orc.make_state_dict(shp, seed=0)
     m = mm.MIDIModel(mm.MIDIModelConfig.from_name("tv2o-medium"))
     m.load_state_dict(sd, strict=True)
     m = m.to("cuda", dtype).eval()
-    B, cuts = 2, (0, 300, 512, 641, 642)
+    B = 2
     x = orc.synthetic_events(tok, B, cuts[-1], seed=91)
     torch.set_num_threads(min(os.cpu_count() or 8, 32))
 
