@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass, field
-from typing import Callable, List, Optional
+from typing import Callable, List, NamedTuple, Optional
 
 import os
 
@@ -107,47 +107,59 @@ def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, accumulate
 # --------------------------------------------------------------------------------------------------
 # training / prefill forward
 # --------------------------------------------------------------------------------------------------
-def layer_forward(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable,
-                  kv_out: Optional[list] = None, save: bool = True, lean: bool = False):
-    """One pre-norm LLaMA block (LlamaDecoderLayer.forward, TF:models/llama/modeling_llama.py:295-324) on x [nseq*slen, D]:
-    RMSNorm -> q|k|v projection -> RoPE -> causal attention -> o projection + residual -> RMSNorm -> gate|up projection with
-    SwiGLU epilogue -> down projection + residual.  8 launches for the event-level stack in bf16 (bench.py --mode block times
-    exactly this function).  ``save=False`` is the forward-only form (prompt prefill, validation): gate|up is never written,
-    only the activation.  ``lean`` (with save): the SwiGLU activation ``a`` is not kept -- the backward recomputes it from the
-    stored gate|up with mh_swiglu_fwd, bit for bit (the fused epilogue and that kernel share their roundings) -- which takes
-    I of the 8 D + 3 I saved elements per row off the activation memory (the 2x-hidden large shape at 16 x 4096 per GPU: 39 GB).
-    Returns (block output, tensors the backward needs | None)."""
+class LayerSaved(NamedTuple):
+    """what one block keeps for its backward"""
+    x: torch.Tensor                 # block input (the residual stream)
+    rstd1: torch.Tensor
+    h1: Optional[torch.Tensor]      # norm1(x); None in the folded form
+    qkv: torch.Tensor
+    o: torch.Tensor
+    lse: Optional[torch.Tensor]     # event-level stack only
+    x2: torch.Tensor                # residual stream after the attention half
+    rstd2: torch.Tensor
+    h2: Optional[torch.Tensor]      # norm2(x2); None in the folded form
+    gu: torch.Tensor
+    a: Optional[torch.Tensor]       # SwiGLU activation; None when lean (the backward recomputes it from gu)
+
+
+class StackSaved(NamedTuple):
+    """what stack_forward(save=True) hands to stack_backward"""
+    layers: List[Optional[LayerSaved]]   # (a list: stack_backward releases each entry once its layer is done)
+    x_last: torch.Tensor                 # input of the final RMSNorm
+    rstdf: torch.Tensor
+    nseq: int
+    slen: int
+    folded: Optional[list]               # the folded weights the forward ran with; None: the plain blocks
+
+
+def _norm_qkv(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, slen: int, rope: RopeTable, pos0: int, rope_in_attn: bool,
+              stats: bool):
+    """First half of the plain block up to the attention: RMSNorm -> q|k|v projection, rotated at positions [pos0, pos0 + slen)
+    unless ``rope_in_attn``.  ``stats``: the norm also stores rstd.  Returns (h1, rstd1 | None, qkv)."""
     M, D = x.shape
-    H, I = spec.H, spec.I
     h1 = _empty((M, D), x)
-    rstd1 = _empty((M,), x, torch.float32)
+    rstd1 = _empty((M,), x, torch.float32) if stats else None
     ops.rmsnorm_fwd(x, lw.n1, h1, rstd1, spec.eps)
     qkv = _empty((M, 3 * D), x)
-    # token-level stack: RoPE is applied inside the attention kernels (q,k of a (sequence, head) are in registers
-    # there anyway), so qkv stays unrotated -- except for a prefill, whose K rows go to the cache rotated.
-    # event-level stack (heads of 64): RoPE rides on the q|k|v projection's epilogue.
-    rope_in_attn = spec.kind != "event" and kv_out is None
     if not rope_in_attn and ops.rope_fused_ok(h1, spec.hd):
-        ops.gemm_rope(h1, lw.wqkv, qkv, rope.fused(), slen, 0, spec.hd)
+        ops.gemm_rope(h1, lw.wqkv, qkv, rope.fused(), slen, pos0, spec.hd)
     else:
         ops.gemm_nt(h1, lw.wqkv, qkv)
         if not rope_in_attn:
-            ops.rope_(qkv, rope.cos, rope.sin, slen, 0, H, spec.hd, +1)
-    o = _empty((M, D), x)
-    lse = None
-    if spec.kind == "event":
-        lse = _empty((nseq * H * ops.round_up(slen, 64),), x, torch.float32)
-        ops.attn_fwd(qkv, o, lse, nseq, slen, H, spec.scale)
-    elif rope_in_attn:
-        ops.tokattn_fwd(qkv, o, nseq, slen, H, spec.scale, rope.cos, rope.sin)
-    else:
-        ops.tokattn_fwd(qkv, o, nseq, slen, H, spec.scale)
-    if kv_out is not None:
-        kv_out.append(qkv)
+            ops.rope_(qkv, rope.cos, rope.sin, slen, pos0, spec.H, spec.hd, +1)
+    return h1, rstd1, qkv
+
+
+def _o_mlp(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, o: torch.Tensor, save: bool, stats: bool):
+    """Second half of the plain block, behind the attention: o projection + residual -> RMSNorm -> gate|up projection with
+    SwiGLU -> down projection + residual.  ``save``: gate|up is written as well as the activation.  ``stats`` as in _norm_qkv.
+    Returns (x3, x2, rstd2 | None, h2, gu | None, a)."""
+    M, D = x.shape
+    I = spec.I
     x2 = _empty((M, D), x)
     ops.gemm_nt(o, lw.wo, x2, beta=1.0, res=x)
     h2 = _empty((M, D), x)
-    rstd2 = _empty((M,), x, torch.float32)
+    rstd2 = _empty((M,), x, torch.float32) if stats else None
     ops.rmsnorm_fwd(x2, lw.n2, h2, rstd2, spec.eps)
     a = _empty((M, I), x)
     gu = None
@@ -161,7 +173,40 @@ def layer_forward(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, nseq: int,
         ops.swiglu_fwd(gu, a)
     x3 = _empty((M, D), x)
     ops.gemm_nt(a, lw.wd, x3, beta=1.0, res=x2)
-    return x3, ((x, rstd1, h1, qkv, o, lse, x2, rstd2, h2, gu, None if lean else a) if save else None)
+    return x3, x2, rstd2, h2, gu, a
+
+
+def layer_forward(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable,
+                  kv_out: Optional[list] = None, save: bool = True, lean: bool = False):
+    """One pre-norm LLaMA block (LlamaDecoderLayer.forward, TF:models/llama/modeling_llama.py:295-324) on x [nseq*slen, D]:
+    RMSNorm -> q|k|v projection -> RoPE -> causal attention -> o projection + residual -> RMSNorm -> gate|up projection with
+    SwiGLU epilogue -> down projection + residual.  7 launches for the event-level stack in bf16, where RoPE rides on the q|k|v
+    projection (8 where it is a launch of its own; bench.py --mode block times exactly this function).  ``save=False`` is the
+    forward-only form (prompt prefill, validation): gate|up is never written, only the activation.  ``lean`` (with save): the
+    SwiGLU activation ``a`` is not kept -- the backward recomputes it from the
+    stored gate|up with mh_swiglu_fwd, bit for bit (the fused epilogue and that kernel share their roundings) -- which takes
+    I of the 8 D + 3 I saved elements per row off the activation memory (the 2x-hidden large shape at 16 x 4096 per GPU: 39 GB).
+    Returns (block output, LayerSaved | None)."""
+    M, D = x.shape
+    H = spec.H
+    # token-level stack: RoPE is applied inside the attention kernels (q,k of a (sequence, head) are in registers
+    # there anyway), so qkv stays unrotated -- except for a prefill, whose K rows go to the cache rotated.
+    # event-level stack (heads of 64): RoPE rides on the q|k|v projection's epilogue.
+    rope_in_attn = spec.kind != "event" and kv_out is None
+    h1, rstd1, qkv = _norm_qkv(spec, lw, x, slen, rope, 0, rope_in_attn, stats=True)
+    o = _empty((M, D), x)
+    lse = None
+    if spec.kind == "event":
+        lse = _empty((nseq * H * ops.round_up(slen, 64),), x, torch.float32)
+        ops.attn_fwd(qkv, o, lse, nseq, slen, H, spec.scale)
+    elif rope_in_attn:
+        ops.tokattn_fwd(qkv, o, nseq, slen, H, spec.scale, rope.cos, rope.sin)
+    else:
+        ops.tokattn_fwd(qkv, o, nseq, slen, H, spec.scale)
+    if kv_out is not None:
+        kv_out.append(qkv)
+    x3, x2, rstd2, h2, gu, a = _o_mlp(spec, lw, x, o, save, stats=True)
+    return x3, (LayerSaved(x, rstd1, h1, qkv, o, lse, x2, rstd2, h2, gu, None if lean else a) if save else None)
 
 
 # The forward-only event-level block with both RMSNorms folded around its projections (r05): below these row counts the two
@@ -172,63 +217,23 @@ FOLD_MIN_ROWS_ON_THE_FLY = 131072   # (12 layers: the fold ~0.7 ms of elementwis
 
 
 def layer_forward_folded(spec: StackSpec, lw: LayerTensors, fold, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable,
-                         parts_in: Optional[torch.Tensor], kv_out: Optional[list] = None):
-    """layer_forward(save=False) without its two RMSNorm passes (LlamaDecoderLayer.forward, TF:models/llama/modeling_llama.py:295-324;
+                         parts_in: Optional[torch.Tensor], kv_out: Optional[list] = None, saved_out: Optional[list] = None,
+                         lean: bool = False):
+    """layer_forward without its two RMSNorm passes (LlamaDecoderLayer.forward, TF:models/llama/modeling_llama.py:295-324;
     LlamaRMSNorm :62-67): ``fold`` = (wqkv * n1, wgu * n2) from fold_norm_weights, so norm(x) W^T = rstd (.) (x W'^T) and the
-    normalised activations h1 / h2 are never written or read.  The row statistics come out of the PRODUCING projections: the
+    normalised activations h1 / h2 are never written, read or kept (training: a fifth of the saved activations less per layer).
+    The row statistics come out of the PRODUCING projections: the
     o and down projections (mh_gemm_rowss) leave per-64-column sums of squares of the rows they store (``parts`` [D/64, M]),
     mh_row_rstd turns them into rstd (one tiny launch), the q|k|v + RoPE and gate|up + SwiGLU projections apply it to their
     fp32 accumulators before their own epilogue arithmetic.  7 launches, none of them a pass over the residual stream.
     ``parts_in``: the statistics of ``x`` left by the previous block's down projection (None: computed from x itself).
+    ``saved_out`` (training, r06; a list as ``kv_out`` is): receives the block's LayerSaved for layer_backward_folded, ``lean`` as in
+    layer_forward; gate|up is written, and each half gets its own rstd.  The token-level stack takes this form in training only:
+    RoPE stays inside its attention kernel, the q|k|v projection is the plain GEMM with a row scale.
     Returns (block output, its parts)."""
     M, D = x.shape
     H, I = spec.H, spec.I
-    wq_n, wgu_n = fold
-    rstd = _empty((M,), x, torch.float32)
-    if parts_in is not None:
-        ops.row_rstd(rstd, D, spec.eps, parts=parts_in)
-    else:
-        ops.row_rstd(rstd, D, spec.eps, x=x)
-    qkv = _empty((M, 3 * D), x)
-    ops.gemm_rope(x, wq_n, qkv, rope.fused(), slen, 0, spec.hd, rowscale=rstd)
-    o = _empty((M, D), x)
-    lse = _empty((nseq * H * ops.round_up(slen, 64),), x, torch.float32)
-    ops.attn_fwd(qkv, o, lse, nseq, slen, H, spec.scale)
-    if kv_out is not None:
-        kv_out.append(qkv)
-    parts = _empty((D // 64, M), x, torch.float32)
-    x2 = _empty((M, D), x)
-    ops.gemm_rowss(o, lw.wo, x2, parts, res=x)
-    ops.row_rstd(rstd, D, spec.eps, parts=parts)
-    a = _empty((M, I), x)
-    ops.gemm_swiglu(x2, wgu_n, None, a, rowscale=rstd)
-    x3 = _empty((M, D), x)
-    ops.gemm_rowss(a, lw.wd, x3, parts, res=x2)
-    return x3, parts
-
-
-def train_fold_ok(spec: StackSpec, x: torch.Tensor) -> bool:
-    """whether the TRAINING forward / backward of stack ``spec`` over the rows ``x`` can run with its RMSNorms folded around
-    the projections (layer_forward_train_folded / layer_backward_folded): bf16 on the production GEMM with its K-step-64 loops,
-    the fused SwiGLU epilogues in both directions, whole 64-column statistics chunks, 4-row groups, and -- event-level stack --
-    the RoPE epilogue and the one-call attention backward"""
-    ok = (x.dtype == torch.bfloat16 and ops.swiglu_fused_ok(x, spec.I) and ops.dswiglu_ok(x, spec.I) and spec.D % 64 == 0
-          and x.shape[0] % 4 == 0 and ops.get_option("gemm_k64") == 1 and os.environ.get("MH_NORM_FOLD_TRAIN", "1") != "0")
-    if ok and spec.kind == "event":
-        ok = ops.rope_fused_ok(x, spec.hd) and ops.attn_bwd_scaled_ok(x)
-    return ok
-
-
-def layer_forward_train_folded(spec: StackSpec, lw: LayerTensors, fold, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable,
-                               parts_in: Optional[torch.Tensor], lean: bool = False):
-    """layer_forward(save=True) with both RMSNorms folded around the projections (r06; LlamaDecoderLayer.forward,
-    TF:models/llama/modeling_llama.py:295-324, LlamaRMSNorm :62-67): the q|k|v and gate|up projections read the residual stream
-    itself against ``fold`` = (wqkv * n1, wgu * n2) and scale their rows by rstd, whose statistics the PRODUCING projections (o,
-    down: mh_gemm_rowss) leave behind.  The normalised activations h1 / h2 are never written, read or kept: two passes over the
-    residual stream and a fifth of the saved activations less per layer.  Both stacks (token-level: RoPE stays inside the attention
-    kernel, the q|k|v projection is the plain GEMM with a row scale).  Returns (output, its statistics, what the backward needs)."""
-    M, D = x.shape
-    H, I = spec.H, spec.I
+    save = saved_out is not None
     wq_n, wgu_n = fold
     rstd1 = _empty((M,), x, torch.float32)
     if parts_in is not None:
@@ -245,161 +250,181 @@ def layer_forward_train_folded(spec: StackSpec, lw: LayerTensors, fold, x: torch
     else:
         ops.gemm_nt_scaled(x, wq_n, qkv, rstd1)
         ops.tokattn_fwd(qkv, o, nseq, slen, H, spec.scale, rope.cos, rope.sin)
+    if kv_out is not None:
+        kv_out.append(qkv)
     parts = _empty((D // 64, M), x, torch.float32)
     x2 = _empty((M, D), x)
     ops.gemm_rowss(o, lw.wo, x2, parts, res=x)
-    rstd2 = _empty((M,), x, torch.float32)
+    # forward-only: one rstd and one parts buffer serve both halves
+    rstd2 = _empty((M,), x, torch.float32) if save else rstd1
     ops.row_rstd(rstd2, D, spec.eps, parts=parts)
-    gu = _empty((M, 2 * I), x)
+    gu = _empty((M, 2 * I), x) if save else None
     a = _empty((M, I), x)
     ops.gemm_swiglu(x2, wgu_n, gu, a, rowscale=rstd2)
-    parts3 = _empty((D // 64, M), x, torch.float32)
+    parts3 = _empty((D // 64, M), x, torch.float32) if save else parts
     x3 = _empty((M, D), x)
     ops.gemm_rowss(a, lw.wd, x3, parts3, res=x2)
-    return x3, parts3, (x, rstd1, qkv, o, lse, x2, rstd2, gu, None if lean else a)
+    if save:
+        saved_out.append(LayerSaved(x, rstd1, None, qkv, o, lse, x2, rstd2, None, gu, None if lean else a))
+    return x3, parts3
 
 
-def layer_backward_folded(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, fold, keep, dx: torch.Tensor, nseq: int, slen: int,
-                          rope: RopeTable, accumulate: bool) -> torch.Tensor:
-    """The backward of layer_forward_train_folded.  With z = x W'^T, y = rstd (.) z: the producers of d y store d z = rstd (.) d y
+def train_fold_ok(spec: StackSpec, x: torch.Tensor) -> bool:
+    """whether the TRAINING forward / backward of stack ``spec`` over the rows ``x`` can run with its RMSNorms folded around
+    the projections (layer_forward_folded / layer_backward_folded): bf16 on the production GEMM with its K-step-64 loops,
+    the fused SwiGLU epilogues in both directions, whole 64-column statistics chunks, 4-row groups, and -- event-level stack --
+    the RoPE epilogue and the one-call attention backward"""
+    ok = (x.dtype == torch.bfloat16 and ops.swiglu_fused_ok(x, spec.I) and ops.dswiglu_ok(x, spec.I) and spec.D % 64 == 0
+          and x.shape[0] % 4 == 0 and ops.get_option("gemm_k64") == 1 and os.environ.get("MH_NORM_FOLD_TRAIN", "1") != "0")
+    if ok and spec.kind == "event":
+        ok = ops.rope_fused_ok(x, spec.hd) and ops.attn_bwd_scaled_ok(x)
+    return ok
+
+
+def runs_folded(spec: StackSpec, x: torch.Tensor, save: bool, kv_out: Optional[list], fold_kept: bool) -> bool:
+    """Whether stack_forward over the rows ``x`` runs the folded blocks -- the one place that decides it; ``fold_kept``: the caller
+    has (or would pass) folded weights it keeps current.  A training forward (``save``) folds only with kept weights -- the backward
+    needs this step's -- and where train_fold_ok holds; a forward-only pass of the event-level stack folds from
+    FOLD_MIN_ROWS_PREFOLDED rows up with kept weights, and from FOLD_MIN_ROWS_ON_THE_FLY up without, deriving them per call."""
+    if save:
+        return fold_kept and kv_out is None and train_fold_ok(spec, x)
+    return (spec.kind == "event" and x.shape[0] >= (FOLD_MIN_ROWS_PREFOLDED if fold_kept else FOLD_MIN_ROWS_ON_THE_FLY)
+            and ops.norm_fold_ok(x, spec.D, spec.hd, spec.I))
+
+
+def layer_backward(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, keep: LayerSaved, dx: torch.Tensor, nseq: int, slen: int,
+                   rope: RopeTable, accumulate: bool) -> torch.Tensor:
+    """The backward of layer_forward: dx = d loss / d block output -> d loss / d block input (written over ``dx``), the layer's
+    parameter gradients to ``lg``."""
+    M, D = dx.shape
+    H, I = spec.H, spec.I
+    # ---- MLP ----
+    a = keep.a
+    if a is None:                                   # lean forward: a = round(silu(gate)) * up again, from the stored gate|up
+        a = _empty((M, I), dx)
+        ops.swiglu_fwd(keep.gu, a)
+    dgu = _empty((M, 2 * I), dx)
+    if ops.dswiglu_ok(dx, I):                       # d a = dx @ wd with the SwiGLU backward as its epilogue
+        ops.gemm_dswiglu(dx, lw.wd, keep.gu, dgu)
+    else:
+        da = _empty((M, I), dx)
+        ops.gemm_nt(dx, lw.wd, da, tb=True)         # d a = dx @ wd      (wd [D, I] read contraction-major)
+        ops.swiglu_bwd(keep.gu, da, dgu)
+        del da
+    linear_wgrad(dx, a, lg.wd, accumulate)
+    del a
+    dh2 = _empty((M, D), dx)
+    ops.gemm_nt(dgu, lw.wgu, dh2, tb=True)          # d h2 = dgu @ wgu
+    linear_wgrad(dgu, keep.h2, lg.wgu, accumulate)
+    del dgu
+    dx2 = _empty((M, D), dx)
+    ops.rmsnorm_bwd(keep.x2, lw.n2, keep.rstd2, dh2, dx, dx2, lg.n2, accumulate)
+    # ---- attention ----
+    do = dh2                                        # reuse
+    ops.gemm_nt(dx2, lw.wo, do, tb=True)            # d o = dx2 @ wo
+    linear_wgrad(dx2, keep.o, lg.wo, accumulate)
+    dqkv = _empty((M, 3 * D), dx)
+    if spec.kind == "event":
+        ops.attn_bwd(keep.qkv, keep.o, do, keep.lse, dqkv, nseq, slen, H, spec.scale, rope.cos, rope.sin)  # (rotated back in the stores)
+    else:  # (saved qkv is unrotated: the forward ran with save=True, never as a prefill)
+        ops.tokattn_bwd(keep.qkv, do, dqkv, nseq, slen, H, spec.scale, rope.cos, rope.sin)
+    dh1 = do
+    ops.gemm_nt(dqkv, lw.wqkv, dh1, tb=True)        # d h1 = dqkv @ wqkv
+    linear_wgrad(dqkv, keep.h1, lg.wqkv, accumulate)
+    del dqkv
+    ops.rmsnorm_bwd(keep.x, lw.n1, keep.rstd1, dh1, dx2, dx, lg.n1, accumulate)
+    return dx
+
+
+def layer_backward_folded(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, fold, keep: LayerSaved, dx: torch.Tensor, nseq: int,
+                          slen: int, rope: RopeTable, accumulate: bool) -> torch.Tensor:
+    """The backward of layer_forward_folded.  With z = x W'^T, y = rstd (.) z: the producers of d y store d z = rstd (.) d y
     (the SwiGLU-backward epilogue, the attention backward's stores), t = d z W' is the dgrad on the folded weights,
     dx = t - x (rstd^2 / D) rowdot(t, x) + dres the norm's backward without its weight, and the weight gradient G' = d z^T x
     turns into dW = G' (.) w and dw = colsum(G' (.) W) inside its split-K reduction (ops.wgrad_folded)."""
-    x, rstd1, qkv, o, lse, x2, rstd2, gu, a = keep
     M, D = dx.shape
     H, I = spec.H, spec.I
     wq_n, wgu_n = fold
     # ---- MLP ----
+    a = keep.a
     if a is None:
         a = _empty((M, I), dx)
-        ops.swiglu_fwd(gu, a)
+        ops.swiglu_fwd(keep.gu, a)
     dz2 = _empty((M, 2 * I), dx)
-    ops.gemm_dswiglu(dx, lw.wd, gu, dz2, rowscale=rstd2)     # rstd2 (.) SwiGLU'(gate|up) (dx @ wd)
+    ops.gemm_dswiglu(dx, lw.wd, keep.gu, dz2, rowscale=keep.rstd2)     # rstd2 (.) SwiGLU'(gate|up) (dx @ wd)
     linear_wgrad(dx, a, lg.wd, accumulate)
     del a
     t2 = _empty((M, D), dx)
     ops.gemm_nt(dz2, wgu_n, t2, tb=True)                     # t2 = d z2 @ W'gu
-    ops.wgrad_folded(dz2, x2, lg.wgu, lw.n2, lw.wgu, lg.n2, accumulate)
+    ops.wgrad_folded(dz2, keep.x2, lg.wgu, lw.n2, lw.wgu, lg.n2, accumulate)
     del dz2
     dx2 = _empty((M, D), dx)
-    ops.rmsnorm_bwd_folded(x2, rstd2, t2, dx, dx2)
+    ops.rmsnorm_bwd_folded(keep.x2, keep.rstd2, t2, dx, dx2)
     # ---- attention ----
     do = t2                                                  # reuse
     ops.gemm_nt(dx2, lw.wo, do, tb=True)
-    linear_wgrad(dx2, o, lg.wo, accumulate)
+    linear_wgrad(dx2, keep.o, lg.wo, accumulate)
     dz1 = _empty((M, 3 * D), dx)
     if spec.kind == "event":
-        ops.attn_bwd(qkv, o, do, lse, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=rstd1)
+        ops.attn_bwd(keep.qkv, keep.o, do, keep.lse, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
     else:
-        ops.tokattn_bwd(qkv, do, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=rstd1)
+        ops.tokattn_bwd(keep.qkv, do, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
     t1 = do
     ops.gemm_nt(dz1, wq_n, t1, tb=True)                      # t1 = d z1 @ W'qkv
-    ops.wgrad_folded(dz1, x, lg.wqkv, lw.n1, lw.wqkv, lg.n1, accumulate)
+    ops.wgrad_folded(dz1, keep.x, lg.wqkv, lw.n1, lw.wqkv, lg.n1, accumulate)
     del dz1
-    ops.rmsnorm_bwd_folded(x, rstd1, t1, dx2, dx)
+    ops.rmsnorm_bwd_folded(keep.x, keep.rstd1, t1, dx2, dx)
     return dx
 
 
 def stack_forward(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable,
                   save: bool, kv_out: Optional[list] = None, lean: bool = False, folded=None):
-    """x [nseq*slen, D] (inputs_embeds) -> last_hidden_state [nseq*slen, D].
+    """x [nseq*slen, D] (inputs_embeds) -> (last_hidden_state [nseq*slen, D], StackSaved | None).
     save=True keeps what the backward needs (``lean``: minus the SwiGLU activations, recomputed in the backward);
-    kv_out (prefill) receives each layer's post-RoPE qkv.  Forward-only passes of the event-level stack over enough rows run
-    the folded-norm blocks (layer_forward_folded); ``folded`` = fold_norm_weights(W) kept current by the caller (a decode
-    session's), otherwise the fold is made here, from the live weights, per call."""
+    kv_out (prefill) receives each layer's post-RoPE qkv.  runs_folded picks the blocks: plain (layer_forward) or with the
+    RMSNorms folded (layer_forward_folded).  ``folded`` = fold_norm_weights(W) kept current by the caller (a decode session's;
+    MIDIModel.folded_weights, re-derived after every update -- the training forward takes no other, and the backward finds them
+    in the context); a forward-only pass without one makes the fold here, from the live weights, per call."""
     _check_heads(spec)
     M, D = x.shape
     assert M == nseq * slen
     rope.ensure(slen)
-    if (not save and spec.kind == "event" and M >= (FOLD_MIN_ROWS_PREFOLDED if folded is not None else FOLD_MIN_ROWS_ON_THE_FLY)
-            and ops.norm_fold_ok(x, D, spec.hd, spec.I)):
+    if runs_folded(spec, x, save, kv_out, folded is not None):
         if folded is None:
             folded = fold_norm_weights(W)
-        parts = None
-        for lw, fold in zip(W.layers, folded):
-            x, parts = layer_forward_folded(spec, lw, fold, x, nseq, slen, rope, parts, kv_out)
-        y = _empty((M, D), x)
-        ops.rmsnorm_fwd(x, W.norm, y, None, spec.eps)
-        return y, None
-    saved = []
-    if save and folded is not None and kv_out is None and train_fold_ok(spec, x):
-        # the TRAINING forward with folded RMSNorms (r06): ``folded`` = the weights of this step (the caller re-derives them after
-        # every update: MIDIModel.folded_weights); the backward finds them in the context
-        parts = None
-        for lw, fold in zip(W.layers, folded):
-            x, parts, keep = layer_forward_train_folded(spec, lw, fold, x, nseq, slen, rope, parts, lean)
-            saved.append(keep)
-        y = _empty((M, D), x)
-        rstdf = _empty((M,), x, torch.float32)
-        ops.rmsnorm_fwd(x, W.norm, y, rstdf, spec.eps)
-        return y, (saved, x, rstdf, nseq, slen, folded)
-    for lw in W.layers:
-        x3, keep = layer_forward(spec, lw, x, nseq, slen, rope, kv_out, save, lean and save)
-        if save:
-            saved.append(keep)
-        x = x3
+    else:
+        folded = None
+    saved = [] if save else None
+    parts = None
+    for li, lw in enumerate(W.layers):
+        if folded is not None:
+            x, parts = layer_forward_folded(spec, lw, folded[li], x, nseq, slen, rope, parts, kv_out, saved, lean)
+        else:
+            x, keep = layer_forward(spec, lw, x, nseq, slen, rope, kv_out, save, lean and save)
+            if save:
+                saved.append(keep)
     y = _empty((M, D), x)
-    rstdf = _empty((M,), x, torch.float32)
+    # (the forward-only folded pass is the one form that asks the final norm for no rstd)
+    rstdf = _empty((M,), x, torch.float32) if save or folded is None else None
     ops.rmsnorm_fwd(x, W.norm, y, rstdf, spec.eps)
-    return y, ((saved, x, rstdf, nseq, slen) if save else None)
+    return y, (StackSaved(saved, x, rstdf, nseq, slen, folded) if save else None)
 
 
-def stack_backward(spec: StackSpec, W: StackTensors, G: StackTensors, ctx, dy: torch.Tensor,
+def stack_backward(spec: StackSpec, W: StackTensors, G: StackTensors, ctx: StackSaved, dy: torch.Tensor,
                    rope: RopeTable, accumulate: bool, on_layer_done: Optional[Callable[[int], None]] = None):
     """dy = d loss / d last_hidden_state  ->  d loss / d inputs_embeds; parameter gradients go to G
     (overwritten, or added to when `accumulate`).  `on_layer_done(i)` fires when layer i's gradients are
     final (layers finish in reverse order) — the data-parallel reducer hangs its bucket launches on it."""
-    folded = ctx[5] if len(ctx) > 5 else None
-    saved, x_last, rstdf, nseq, slen = ctx[:5]
     M, D = dy.shape
-    H, I = spec.H, spec.I
     dx = _empty((M, D), dy)
-    ops.rmsnorm_bwd(x_last, W.norm, rstdf, dy, None, dx, G.norm, accumulate)
-    if folded is not None:  # the forward ran layer_forward_train_folded
-        for li in range(len(W.layers) - 1, -1, -1):
-            dx = layer_backward_folded(spec, W.layers[li], G.layers[li], folded[li], saved[li], dx, nseq, slen, rope, accumulate)
-            saved[li] = None
-            if on_layer_done is not None:
-                on_layer_done(li)
-        return dx
+    ops.rmsnorm_bwd(ctx.x_last, W.norm, ctx.rstdf, dy, None, dx, G.norm, accumulate)
     for li in range(len(W.layers) - 1, -1, -1):
         lw, lg = W.layers[li], G.layers[li]
-        x, rstd1, h1, qkv, o, lse, x2, rstd2, h2, gu, a = saved[li]
-        # ---- MLP ----
-        if a is None:                                   # lean forward: a = round(silu(gate)) * up again, from the stored gate|up
-            a = _empty((M, I), dy)
-            ops.swiglu_fwd(gu, a)
-        dgu = _empty((M, 2 * I), dy)
-        if ops.dswiglu_ok(dx, I):                       # d a = dx @ wd with the SwiGLU backward as its epilogue
-            ops.gemm_dswiglu(dx, lw.wd, gu, dgu)
+        if ctx.folded is not None:
+            dx = layer_backward_folded(spec, lw, lg, ctx.folded[li], ctx.layers[li], dx, ctx.nseq, ctx.slen, rope, accumulate)
         else:
-            da = _empty((M, I), dy)
-            ops.gemm_nt(dx, lw.wd, da, tb=True)         # d a = dx @ wd      (wd [D, I] read contraction-major)
-            ops.swiglu_bwd(gu, da, dgu)
-            del da
-        linear_wgrad(dx, a, lg.wd, accumulate)
-        del a
-        dh2 = _empty((M, D), dy)
-        ops.gemm_nt(dgu, lw.wgu, dh2, tb=True)          # d h2 = dgu @ wgu
-        linear_wgrad(dgu, h2, lg.wgu, accumulate)
-        del dgu
-        dx2 = _empty((M, D), dy)
-        ops.rmsnorm_bwd(x2, lw.n2, rstd2, dh2, dx, dx2, lg.n2, accumulate)
-        # ---- attention ----
-        do = dh2                                        # reuse
-        ops.gemm_nt(dx2, lw.wo, do, tb=True)            # d o = dx2 @ wo
-        linear_wgrad(dx2, o, lg.wo, accumulate)
-        dqkv = _empty((M, 3 * D), dy)
-        if spec.kind == "event":
-            ops.attn_bwd(qkv, o, do, lse, dqkv, nseq, slen, H, spec.scale, rope.cos, rope.sin)  # (rotated back in the stores)
-        else:  # (saved qkv is unrotated: the forward ran with save=True, never as a prefill)
-            ops.tokattn_bwd(qkv, do, dqkv, nseq, slen, H, spec.scale, rope.cos, rope.sin)
-        dh1 = do
-        ops.gemm_nt(dqkv, lw.wqkv, dh1, tb=True)        # d h1 = dqkv @ wqkv
-        linear_wgrad(dqkv, h1, lg.wqkv, accumulate)
-        del dqkv
-        ops.rmsnorm_bwd(x, lw.n1, rstd1, dh1, dx2, dx, lg.n1, accumulate)
-        saved[li] = None
+            dx = layer_backward(spec, lw, lg, ctx.layers[li], dx, ctx.nseq, ctx.slen, rope, accumulate)
+        ctx.layers[li] = None                           # activations are released back to front
         if on_layer_done is not None:
             on_layer_done(li)
     return dx
@@ -447,27 +472,21 @@ def stack_prefill(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, 
 def stack_extend(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable, kv: KVState):
     """A chunk of ``slen`` > 1 new positions per sequence behind ``kv.len`` cached ones (a cache-carrying forward with q_len > 1:
     chunked prefill, TF:models/llama/modeling_llama.py:386-389 position offset + TF:integrations/sdpa_attention.py:79-166).
-    Per layer: the chunk's q|k|v projection rotated at positions [n, n + slen), K/V appended to the cache, the cached K/V rows
-    gathered in front of the chunk's rows, and the flash forward over the n + slen rows computing the chunk's query tiles only --
-    the same ~9 launches per layer whatever ``slen`` is (the event-by-event form this replaces took 5 x slen).  Event-level
-    stack (heads of 64)."""
+    Per layer the plain block's two halves (_norm_qkv, _o_mlp) around a different middle: the chunk's q|k|v projection rotated at
+    positions [n, n + slen), K/V appended to the cache, the cached K/V rows gathered in front of the chunk's rows, and the flash
+    forward over the n + slen rows computing the chunk's query tiles only -- the same 11 launches per layer in bf16 (7 of the
+    block, K/V store and gather, two torch copies: the chunk's rows into the gathered buffer and its outputs out of the
+    attention's) whatever ``slen`` is (the event-by-event form this replaces took 5 x slen).  Event-level stack (heads of 64)."""
     _check_heads(spec)
     assert spec.kind == "event"
     M, D = x.shape
     assert M == nseq * slen
-    n, H, I, hd = kv.len, spec.H, spec.I, spec.hd
+    n, H, hd = kv.len, spec.H, spec.hd
     stot = n + slen
     kv.reserve(stot)
     rope.ensure(stot)
     for li, lw in enumerate(W.layers):
-        h1 = _empty((M, D), x)
-        ops.rmsnorm_fwd(x, lw.n1, h1, None, spec.eps)
-        qkv = _empty((M, 3 * D), x)
-        if ops.rope_fused_ok(h1, hd):
-            ops.gemm_rope(h1, lw.wqkv, qkv, rope.fused(), slen, n, hd)
-        else:
-            ops.gemm_nt(h1, lw.wqkv, qkv)
-            ops.rope_(qkv, rope.cos, rope.sin, slen, n, H, hd, +1)
+        _, _, qkv = _norm_qkv(spec, lw, x, slen, rope, n, rope_in_attn=False, stats=False)
         ops.kv_store_rows(qkv, kv.k[li], kv.v[li], nseq, slen, H, hd, kv.cap, n)
         full = _empty((nseq * stot, 3 * D), x)
         ops.kv_gather_rows(kv.k[li], kv.v[li], full, nseq, n, stot, H, hd, kv.cap)
@@ -476,20 +495,7 @@ def stack_extend(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, s
         lse = _empty((nseq * H * ops.round_up(stot, 64),), x, torch.float32)
         ops.attn_fwd_tail(full, o_full, lse, nseq, stot, H, spec.scale, n)
         o = o_full.view(nseq, stot, D)[:, n:].reshape(M, D)
-        x2 = _empty((M, D), x)
-        ops.gemm_nt(o, lw.wo, x2, beta=1.0, res=x)
-        h2 = _empty((M, D), x)
-        ops.rmsnorm_fwd(x2, lw.n2, h2, None, spec.eps)
-        a = _empty((M, I), x)
-        if ops.swiglu_fused_ok(h2, I):
-            ops.gemm_swiglu(h2, lw.wgu, None, a)
-        else:
-            gu = _empty((M, 2 * I), x)
-            ops.gemm_nt(h2, lw.wgu, gu)
-            ops.swiglu_fwd(gu, a)
-        x3 = _empty((M, D), x)
-        ops.gemm_nt(a, lw.wd, x3, beta=1.0, res=x2)
-        x = x3
+        x = _o_mlp(spec, lw, x, o, save=False, stats=False)[0]
     kv.len = stot
     y = _empty((M, D), x)
     ops.rmsnorm_fwd(x, W.norm, y, None, spec.eps)

@@ -376,9 +376,7 @@ class MIDIModel(nn.Module):
 
     def _folded_for(self, spec, e: torch.Tensor):
         """the kept folded weights when a forward-only pass over ``e`` [rows, D] will run the folded-norm blocks, else None"""
-        if e.shape[0] >= engine.FOLD_MIN_ROWS_PREFOLDED and ops.norm_fold_ok(e, spec.D, spec.hd, spec.I):
-            return self.folded_weights(spec.name)
-        return None
+        return self.folded_weights(spec.name) if engine.runs_folded(spec, e, False, None, True) else None
 
     def forward_token(self, hidden_state=None, x=None, cache=None) -> torch.Tensor:
         """hidden_state (N, n_embd) and/or x (N, t) int64 -> logits (N, [1]+t, vocab)   [midi_model.py:116-135]"""

@@ -92,14 +92,20 @@ def get_option(name: str) -> int:
     return lib().cdll.mh_get_option(name.encode())
 
 
+def _attn_v3() -> int:
+    """the calling thread's "attn_v3" option, read from the library once and then followed through set_option"""
+    if _tl.attn_v3 is None:
+        _tl.attn_v3 = get_option("attn_v3")
+    return _tl.attn_v3
+
+
 def _pick_splitk(M: int, N: int, K: int) -> int:
     """Split the contraction when the output has too few tiles to fill 256 CUs (the weight-gradient shapes):
     aim at >= 512 workgroups, keep >= 512 contraction elements per slice."""
-    if _tl.gemm_variant is None:
-        _tl.gemm_variant = lib().cdll.mh_get_option(b"gemm")
-    bm = bn = 256 if _tl.gemm_variant != 0 else 128
+    variant = get_option("gemm")
+    bm = bn = 256 if variant != 0 else 128
     tiles = ((M + bm - 1) // bm) * ((N + bn - 1) // bn)
-    per_cu = 1 if _tl.gemm_variant != 0 else 2   # resident workgroups per CU of the active kernel
+    per_cu = 1 if variant != 0 else 2   # resident workgroups per CU of the active kernel
     if tiles >= 192 * per_cu or K < 1024:
         return 1
     # fill the 256 CUs once (or twice for the two-per-CU kernel) but never spill a few workgroups into an extra
@@ -536,10 +542,8 @@ def attn_fwd(qkv, o, lse, B: int, S: int, H: int, scale: float):
     # (A/B runs: the environment variables MH_ATTN_V3 / MH_ATTN_V3_WPS set every host thread's initial value inside the
     #  library; set_option / mh_set_option act on the CALLING thread only -- autograd's backward runs on its own thread, so an
     #  A/B of a backward kernel through loss.backward() goes by the environment, or calls ops.attn_bwd directly)
-    if _tl.attn_v3 is None:
-        _tl.attn_v3 = get_option("attn_v3")
     vt = None
-    if qkv.dtype == torch.bfloat16 and (_tl.attn_v3 & 17) != 17:
+    if qkv.dtype == torch.bfloat16 and (_attn_v3() & 17) != 17:
         Sp = round_up(S, 64)
         vt = torch.empty((B * H * 64 * Sp,), dtype=qkv.dtype, device=qkv.device)
         lib().call("mh_attn_prep_fwd", _p(qkv), _p(vt), B, S, H, dt(qkv), _stream())
@@ -549,18 +553,15 @@ def attn_fwd(qkv, o, lse, B: int, S: int, H: int, scale: float):
 
 def attn_bwd_scaled_ok(qkv: torch.Tensor) -> bool:
     """whether attn_bwd serves ``rowscale`` (the one-call third form of the bf16 backward kernels)"""
-    if _tl.attn_v3 is None:
-        _tl.attn_v3 = get_option("attn_v3")
-    return qkv.dtype == torch.bfloat16 and (_tl.attn_v3 & 46) == 46
+    return qkv.dtype == torch.bfloat16 and (_attn_v3() & 46) == 46
 
 
 def attn_bwd(qkv, o, dout, lse, dqkv, B: int, S: int, H: int, scale: float, cos_t=None, sin_t=None, rowscale=None):
     """cos_t/sin_t: return the gradient with respect to the UNROTATED q, k (see mh_attn_bwd); ``rowscale`` (fp32 [B * S]): row m
     of dqkv times rowscale[m] in the kernels' stores (the folded RMSNorm's d z; attn_bwd_scaled_ok)"""
-    if _tl.attn_v3 is None:
-        _tl.attn_v3 = get_option("attn_v3")
     Sp = round_up(S, 64)
-    fused = qkv.dtype == torch.bfloat16 and (_tl.attn_v3 & 14) == 14 and (_tl.attn_v3 & 32) != 0
+    v3 = _attn_v3()
+    fused = qkv.dtype == torch.bfloat16 and (v3 & 14) == 14 and (v3 & 32) != 0
     delta = torch.empty(((2 if fused else 1) * B * H * Sp,), dtype=torch.float32, device=qkv.device)
     if rowscale is not None:
         assert fused and rowscale.shape == (B * S,) and rowscale.dtype == torch.float32 and rowscale.is_contiguous()
@@ -575,7 +576,7 @@ def attn_bwd(qkv, o, dout, lse, dqkv, B: int, S: int, H: int, scale: float, cos_
     qt = kt = dot = None
     # (third form with transpose reads, the default: dQ and dK/dV take Q^T, K^T, dO^T out of the row-major tiles in LDS --
     #  no [B,H,64,Sp] copies, mh_attn_prep_bwd only computes delta)
-    if qkv.dtype == torch.bfloat16 and (_tl.attn_v3 & 14) != 14:
+    if qkv.dtype == torch.bfloat16 and (v3 & 14) != 14:
         n = B * H * 64 * Sp
         buf = torch.empty((3, n), dtype=qkv.dtype, device=qkv.device)
         qt, kt, dot = buf[0], buf[1], buf[2]

@@ -195,7 +195,7 @@ class TrainMIDIModel(MIDIModel):
         # bits, one extra elementwise pass per layer: ~1 % of a step).  For shapes whose activations crowd the 288 GB -- the
         # 2x-hidden large shape at 16 x 4096 per GPU peaks at 306 of 309 GB without it, and RCCL needs room for its channel buffers
         self.lean_activations = False
-        # r06: the training forward / backward with the RMSNorms folded around the projections (engine.layer_forward_train_folded):
+        # r06: the training forward / backward with the RMSNorms folded around the projections (engine.layer_forward_folded with saved_out):
         # no passes over the residual stream for the norms' forward, no normalised activations kept, the norm weights' gradients
         # out of the weight-gradient reductions.  bf16 only (engine.train_fold_ok); False = the r01-r05 schedule.
         self.fold_train_norms = True
@@ -494,11 +494,9 @@ class TrainMIDIModel(MIDIModel):
     def _train_fold(self, spec, rows: torch.Tensor, backward: bool):
         """the folded weights stack_forward should run with: this step's (re-derived after every update) when the training fold
         applies, the kept inference fold for a forward-only pass over enough rows, else None"""
-        if backward:
-            if self.fold_train_norms and self._lora is None and engine.train_fold_ok(spec, rows):
-                return self.folded_weights(spec.name)
+        if backward and (not self.fold_train_norms or self._lora is not None):
             return None
-        return self._folded_for(spec, rows) if spec.kind == "event" else None
+        return self.folded_weights(spec.name) if engine.runs_folded(spec, rows, backward, None, True) else None
 
     def zero_grad(self, set_to_none: bool = False):
         if self._flat_grad is not None:

@@ -2,8 +2,10 @@
 the fused training step + optimiser, the KV-cached decode loop and generate(), all driven through the
 test-only fake backend (tests/emu_ops.py) and checked against the reference-generated golden vectors.
 The same checks run on the real HIP kernels in test_model_gpu.py."""
+import contextlib
 import json
 import os
+import weakref
 
 import numpy as np
 import pytest
@@ -379,7 +381,7 @@ def test_lean_activation_saving_is_bit_identical(orc, tiny, tok):
 
 
 def test_training_fold_of_the_norms_is_the_same_gradient(orc, tiny, tok):
-    """The training step with the RMSNorms folded around the projections (engine.layer_forward_train_folded /
+    """The training step with the RMSNorms folded around the projections (engine.layer_forward_folded with ``saved_out`` /
     layer_backward_folded, r06) against the plain schedule on the same bf16 weights, through the stand-ins: the algebra of the
     fold -- d z = rstd (.) d y from the producers, t = d z W', dx = t - x (rstd^2 / D) rowdot(t, x) + dres, dW = (d z^T x) (.) w,
     dw = colsum((d z^T x) (.) W) -- must give the loss and EVERY gradient tensor of the unfolded graph up to bf16 rounding, the
@@ -417,6 +419,111 @@ def test_training_fold_of_the_norms_is_the_same_gradient(orc, tiny, tok):
         worst = max(worst, 1.0 - cos)
         assert cos > 0.995 and abs(nb / na - 1.0) < 0.05, (k, cos, nb / na)
     assert worst < 5e-3
+
+
+@contextlib.contextmanager
+def record_ops():
+    """emu_ops.install() with every ``ops`` launch logged (the capability questions -- ``*_ok``, get / set_option -- are not
+    launches): one line per call -- the function name, each tensor argument as ``t<n>:dtype[rows x cols]`` where equal ``n`` means the
+    same memory (same data_ptr, storage still alive: buffer reuse such as ``do = t2`` shows), every other argument by value."""
+    log, seen, count = [], {}, [0]
+
+    def show(v):
+        if torch.is_tensor(v):
+            st, hit = v.untyped_storage(), seen.get(v.data_ptr())
+            if hit is None or hit[0]() is not st:
+                count[0] += 1
+                hit = seen[v.data_ptr()] = (weakref.ref(st), count[0])
+            return f"t{hit[1]}:{str(v.dtype)[6:]}[{'x'.join(map(str, v.shape))}]"
+        return "[" + ",".join(map(show, v)) + "]" if isinstance(v, (list, tuple)) else repr(v)
+
+    def logged(name, fn):
+        def call(*a, **k):
+            log.append(f"{name}(" + ", ".join([show(v) for v in a] + [f"{n}={show(v)}" for n, v in sorted(k.items())]) + ")")
+            return fn(*a, **k)
+        return call
+
+    from midi_model_amd import ops
+    with emu_ops.install():
+        real = {n: getattr(ops, n) for n in emu_ops._NAMES if hasattr(ops, n) and not n.endswith("_ok") and not n.endswith("_option")}
+        for n, fn in real.items():
+            setattr(ops, n, logged(n, fn))
+        try:
+            yield log
+        finally:
+            for n, fn in real.items():
+                setattr(ops, n, fn)
+
+
+def test_launch_schedule_of_every_block_form(tiny, monkeypatch):
+    """The sequence of ``ops`` calls of ONE layer in each form the engine has -- plain and folded forward (saving and forward-only),
+    the cache-extending chunk, the three decode bodies, both backwards (lean and not) -- against the lists written out here: the
+    folded and plain forms are otherwise compared only up to bf16 rounding, so a dropped or doubled launch would pass every other
+    host test.  bf16 on the tiny event-level stack (heads of 64: the fused paths).  An ``ops`` call is not always one kernel
+    launch (split-K reductions, re-layouts), so these are schedules, not launch counts."""
+    from midi_model_amd import ops
+    from midi_model_amd.engine import KVState, StackTensors
+    shp, sd, _ = tiny
+    PLAIN = ["rmsnorm_fwd", "gemm_rope", "attn_fwd", "gemm_nt", "rmsnorm_fwd", "gemm_swiglu", "gemm_nt"]
+    FOLDED = ["row_rstd", "gemm_rope", "attn_fwd", "gemm_rowss", "row_rstd", "gemm_swiglu", "gemm_rowss"]
+    EXTEND = ["rmsnorm_fwd", "gemm_rope", "kv_store_rows", "kv_gather_rows", "attn_fwd_tail", "gemm_nt", "rmsnorm_fwd", "gemm_swiglu",
+              "gemm_nt"]
+    DECODE_SKINNY_FOLDED = ["gemm_skinny", "attn_decode_append", "gemm_skinny", "gemm_skinny", "gemm_skinny"]
+    DECODE_SKINNY = ["rmsnorm_fwd", "gemm_skinny", "attn_decode_append", "gemm_skinny", "rmsnorm_fwd", "gemm_skinny", "gemm_skinny"]
+    DECODE_GENERAL = ["rmsnorm_fwd", "gemm_nt", "kv_append", "attn_decode", "gemm_nt", "rmsnorm_fwd", "gemm_nt", "swiglu_fwd", "gemm_nt"]
+    BACKWARD = ["gemm_dswiglu", "gemm_nt", "gemm_nt", "gemm_nt", "rmsnorm_bwd", "gemm_nt", "gemm_nt", "attn_bwd", "gemm_nt", "gemm_nt",
+                "rmsnorm_bwd"]
+    BACKWARD_FOLDED = ["gemm_dswiglu", "gemm_nt", "gemm_nt", "wgrad_folded", "rmsnorm_bwd_folded", "gemm_nt", "gemm_nt", "attn_bwd",
+                       "gemm_nt", "wgrad_folded", "rmsnorm_bwd_folded"]
+    with record_ops() as log:
+        m = TrainMIDIModel(tiny_config())
+        m.load_state_dict(sd)
+        m = m.to(torch.bfloat16)
+        m.grad_buffer()
+        spec, W, rope = m._specs["net"], m._W["net"], m.rope("net")
+        lw, lg, fold = W.layers[0], m._G["net"].layers[0], engine.fold_norm_weights(W)[0]
+        one = StackTensors(embed=W.embed, layers=W.layers[:1], norm=W.norm)
+        nseq, slen = 2, 16
+        rope.ensure(64)
+        x = torch.randn((nseq * slen, spec.D), generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+
+        def run(fn):
+            del log[:]
+            out = fn()
+            return out, [line.split("(")[0] for line in log], [line.split("(")[1].split(", ") for line in log]
+
+        (_, keep), names, args = run(lambda: engine.layer_forward(spec, lw, x, nseq, slen, rope))
+        assert names == PLAIN and args[5][2] != "None"
+        (_, none), names, args = run(lambda: engine.layer_forward(spec, lw, x, nseq, slen, rope, save=False))
+        assert names == PLAIN and none is None and args[5][2] == "None"         # forward-only: gate|up is not written
+        kept = []
+        _, names, args = run(lambda: engine.layer_forward_folded(spec, lw, fold, x, nseq, slen, rope, None, None, kept))
+        assert names == FOLDED and args[0][0] != args[4][0] and args[3][3] != args[6][3] and args[5][2] != "None"
+        _, names, args = run(lambda: engine.layer_forward_folded(spec, lw, fold, x, nseq, slen, rope, None))
+        # forward-only: one rstd and one parts buffer serve both halves
+        assert names == FOLDED and args[0][0] == args[4][0] and args[3][3] == args[6][3] and args[5][2] == "None"
+        for lean in (False, True):
+            pre = ["swiglu_fwd"] if lean else []
+            dx = torch.randn(x.shape, generator=torch.Generator().manual_seed(1)).to(torch.bfloat16)
+            out, names, args = run(lambda: engine.layer_backward(spec, lw, lg, keep._replace(a=None) if lean else keep, dx, nseq, slen,
+                                                                 rope, False))
+            assert names == pre + BACKWARD and out is dx
+            assert args[len(pre) + 5][2] == args[len(pre) + 2][2]                 # d o reuses the buffer of d h2
+            _, names, _ = run(lambda: engine.layer_backward_folded(spec, lw, lg, fold, kept[0]._replace(a=None) if lean else kept[0], dx,
+                                                                   nseq, slen, rope, False))
+            assert names == pre + BACKWARD_FOLDED
+        kv = KVState(spec, nseq, 64, x)
+        engine.stack_prefill(spec, one, x, nseq, slen, rope, kv)
+        _, names, _ = run(lambda: engine.stack_extend(spec, one, x[: nseq * 4], nseq, 4, rope, kv))
+        assert names == EXTEND + ["rmsnorm_fwd"] and kv.len == slen + 4
+        x1 = x[:nseq].contiguous()
+        _, names, _ = run(lambda: engine.stack_decode(spec, one, x1, rope, kv, folded=[fold], final_norm=False))
+        assert names == DECODE_SKINNY_FOLDED
+        _, names, args = run(lambda: engine.stack_decode(spec, one, x1, rope, kv, final_norm=False))
+        assert names == DECODE_SKINNY and args[2][5] == args[0][2] == args[4][2]   # o = h1, h2 = o: one buffer
+        monkeypatch.setattr(ops, "skinny_ok", lambda x, K: False)
+        _, names, _ = run(lambda: engine.stack_decode(spec, one, x1, rope, kv, final_norm=False))
+        assert names == DECODE_GENERAL and kv.len == slen + 4 + 3
 
 
 def test_generate_on_trained_weights_matches_reference(trained, tok):
