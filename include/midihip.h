@@ -312,6 +312,14 @@ int mh_sumsq(const void* g, int64_t n, float* partial1024, float* out, int accum
 int mh_clip_coef(const float* sumsq, float max_norm, float* coef, float* norm, void* stream);
 int mh_adamw(void* p, const void* g, void* m, void* v, int64_t n, float lr, float beta1, float beta2, float eps,
              float weight_decay, float bias_corr1, float bias_corr2, const float* coef_dev, int dtype, void* stream);
+/* Mixed precision (fp32 master weights behind a bf16 working copy).  mh_adamw_master: the same update entirely in fp32 on
+ * p32 / m / v with the gradient read from the fp32 accumulator g32 (scaled by *coef_dev when non-null); in the same pass
+ * p_lo[i] = p32[i] rounded to dtype_lo (MH_BF16; round to nearest even).  All five buffers 16-byte aligned.
+ * mh_grad_fold_f32: dst[i] = float(src[i]), or dst[i] += float(src[i]) with accumulate; `dtype` is the type of src. */
+int mh_adamw_master(float* p32, void* p_lo, const float* g32, float* m, float* v, int64_t n, float lr, float beta1,
+                    float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2, const float* coef_dev,
+                    int dtype_lo, void* stream);
+int mh_grad_fold_f32(const void* src, float* dst, int64_t n, int accumulate, int dtype, void* stream);
 
 /* ---- KV-cached single-event decode (midi_model.py:195-246; TF:cache_utils.py:127-147) -----------------------
  * Cache layout per layer: k,v [B,H,Lmax,hd].  mh_kv_append: rotate q,k of qkv[B,3*H*hd] at position `pos`

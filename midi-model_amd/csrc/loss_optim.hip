@@ -400,6 +400,116 @@ extern "C" int mh_adamw(void* p, const void* g, void* m, void* v, int64_t n, flo
 }
 
 // ---------------------------------------------------------------------------------------------------
+// mixed precision (fp32 master weights behind the bf16 working copy): the same AdamW in fp32 on the master, the moments and
+// the fp32 gradient accumulator, and the bf16 copy of the new master written in the same pass -- 16 B read + 12 B + 2 B
+// written per parameter.  Nothing is rounded between the operations (no rnd<T>): what torch.optim.AdamW computes on fp32
+// tensors.  Eight parameters per lane and trip: 2 x 16 B of each fp32 stream, one 16-byte store of the bf16 copy.
+// ---------------------------------------------------------------------------------------------------
+struct AdamwScalars {
+  float coef, step, sq2, decay, omb1, b2, omb2, eps;
+};
+
+__device__ inline void adamw_master_one(float& p, float g, float& m, float& v, const AdamwScalars& s) {
+  g *= s.coef;
+  p *= s.decay;
+  m = m + (g - m) * s.omb1;
+  v = v * s.b2 + s.omb2 * g * g;
+  const float den = sqrtf(v) / s.sq2 + s.eps;
+  p = p - s.step * (m / den);
+}
+
+__global__ __launch_bounds__(256) void adamw_master_kernel(float* __restrict__ p32, bf16* __restrict__ p_lo,
+                                                           const float* __restrict__ g32, float* __restrict__ m,
+                                                           float* __restrict__ v, int64_t n, float lr, float b1, float b2,
+                                                           float eps, float wd, float bc1, float bc2,
+                                                           const float* __restrict__ coef_dev) {
+  const AdamwScalars s = {coef_dev ? coef_dev[0] : 1.f, lr / bc1, sqrtf(bc2), 1.f - lr * wd, 1.f - b1, b2, 1.f - b2, eps};
+  const int64_t nvec = n / 8;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    const int64_t o = i * 8;
+    Pack<float> pv[2] = {ld16(p32 + o), ld16(p32 + o + 4)}, mv[2] = {ld16(m + o), ld16(m + o + 4)};
+    Pack<float> vv[2] = {ld16(v + o), ld16(v + o + 4)};
+    const Pack<float> gv[2] = {ld16(g32 + o), ld16(g32 + o + 4)};
+    float lo[8];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        float pe = pv[h].get(e), me = mv[h].get(e), ve = vv[h].get(e);
+        adamw_master_one(pe, gv[h].get(e), me, ve, s);
+        pv[h].set(e, pe);
+        mv[h].set(e, me);
+        vv[h].set(e, ve);
+        lo[4 * h + e] = pe;
+      }
+      st16(p32 + o + 4 * h, pv[h]);
+      st16(m + o + 4 * h, mv[h]);
+      st16(v + o + 4 * h, vv[h]);
+    }
+    *reinterpret_cast<bf16x8*>(p_lo + o) = cvt8_bf16(lo);
+  }
+  if (blockIdx.x == 0) {
+    for (int64_t i = nvec * 8 + threadIdx.x; i < n; i += 256) {
+      float pe = p32[i], me = m[i], ve = v[i];
+      adamw_master_one(pe, g32[i], me, ve, s);
+      p32[i] = pe;
+      m[i] = me;
+      v[i] = ve;
+      p_lo[i] = (bf16)pe;
+    }
+  }
+}
+
+extern "C" int mh_adamw_master(float* p32, void* p_lo, const float* g32, float* m, float* v, int64_t n, float lr, float beta1,
+                               float beta2, float eps, float weight_decay, float bias_corr1, float bias_corr2,
+                               const float* coef_dev, int dtype_lo, void* stream) {
+  MH_REQUIRE(n > 0, "adamw_master: empty");
+  MH_REQUIRE(dtype_lo == MH_BF16, "adamw_master: the working copy is bf16 (dtype_lo %d)", dtype_lo);
+  MH_REQUIRE((((uintptr_t)p32 | (uintptr_t)p_lo | (uintptr_t)g32 | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
+             "adamw_master: buffers must be 16-byte aligned");
+  int64_t blocks = (n / 8 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;  // 256 CUs x 8 blocks; the grid-stride loop takes the rest
+  if (blocks < 1) blocks = 1;
+  adamw_master_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(p32, (bf16*)p_lo, g32, m, v, n, lr, beta1, beta2, eps,
+                                                                    weight_decay, bias_corr1, bias_corr2, coef_dev);
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// one micro-batch's gradient into the fp32 accumulator: dst = float(src) or dst += float(src) (exact conversion, one IEEE add)
+template <typename T>
+__global__ __launch_bounds__(256) void grad_fold_f32_kernel(const T* __restrict__ src, float* __restrict__ dst, int64_t n,
+                                                            int accumulate) {
+  constexpr int N = Pack<T>::N;
+  const int64_t nvec = n / N;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * 256) {
+    const Pack<T> sv = ld16(src + i * N);
+#pragma unroll
+    for (int h = 0; h < N / 4; ++h) {
+      float* d = dst + i * N + 4 * h;
+      Pack<float> dv;
+      if (accumulate) dv = ld16(d);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dv.set(e, accumulate ? dv.get(e) + sv.get(4 * h + e) : sv.get(4 * h + e));
+      st16(d, dv);
+    }
+  }
+  if (blockIdx.x == 0)
+    for (int64_t i = nvec * N + threadIdx.x; i < n; i += 256) dst[i] = accumulate ? dst[i] + to_f(src[i]) : to_f(src[i]);
+}
+
+extern "C" int mh_grad_fold_f32(const void* src, float* dst, int64_t n, int accumulate, int dtype, void* stream) {
+  MH_REQUIRE(n > 0, "grad_fold_f32: empty");
+  MH_REQUIRE((((uintptr_t)src | (uintptr_t)dst) & 15) == 0, "grad_fold_f32: buffers must be 16-byte aligned");
+  int64_t blocks = (n / 8 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  DISPATCH_T(dtype, (grad_fold_f32_kernel<T><<<(int)blocks, 256, 0, (hipStream_t)stream>>>((const T*)src, dst, n, accumulate)));
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // sampler front end: probs = softmax(logits / temp) * grammar mask (one wave per row)
 // ---------------------------------------------------------------------------------------------------
 template <typename T>

@@ -22,7 +22,7 @@ from typing import Callable, List, Optional, Tuple
 
 import torch
 
-from . import engine, ops
+from . import engine, mixed, ops
 from .config import MIDIModelConfig
 from .model import MIDIModel
 
@@ -174,8 +174,18 @@ class GradReducer:
 class TrainMIDIModel(MIDIModel):
     def __init__(self, config: MIDIModelConfig, lr=2e-4, weight_decay=0.01, warmup=1e3, max_step=1e6,
                  sample_seq=False, gen_example_interval=1, example_batch=8, accumulate_grad_batches=2,
-                 gradient_clip_val=1.0, ce_chunk_rows=32768, bucket_mb=32):
+                 gradient_clip_val=1.0, ce_chunk_rows=32768, bucket_mb=32, precision=None):
+        """``precision``: the reference's ``--precision`` (train.py:365-371).  ``None`` (default), ``"bf16-true"`` / ``"bf16"`` and
+        ``"32-true"`` / ``"32"`` all mean what this class has always done: the dtype of the model decides, weights, gradients and
+        AdamW moments live in it.  ``"bf16-mixed"``: fp32 master weights behind the bf16 model (mixed.py) -- forward and backward
+        run on the bf16 parameters through the same kernels as bf16-true; the optimiser keeps fp32 parameters of record, accumulates
+        the micro-batch gradients of a window in fp32, clips on the fp32 norm, runs AdamW in fp32 and writes fp32 checkpoints, and
+        after every update the bf16 parameters are the master rounded to nearest even.  That is what the mode shares with
+        Lightning's ``bf16-mixed``; it is NOT bit-parity with it: autocast keeps the embedding output, the residual stream and the
+        norms in fp32, these kernels keep them in bf16.  Any other value (16-mixed, 16-true, 64-true) raises ValueError."""
         super().__init__(config)
+        self.precision = mixed.check_precision(precision)
+        self._mixed = None         # mixed.MixedState once configure_optimizers ran in bf16-mixed
         self.lr, self.weight_decay, self.warmup, self.max_step = lr, weight_decay, warmup, max_step
         self.sample_seq = sample_seq
         self.gen_example_interval, self.example_batch = gen_example_interval, example_batch
@@ -208,6 +218,12 @@ class TrainMIDIModel(MIDIModel):
         'bias' nor 'norm' (train.py:121-151) — in the flat layout that is exactly the matrix region."""
         self._require_gpu()
         flat = self._flat
+        if self.precision == mixed.PRECISION_MIXED:
+            if self._lora is not None:
+                raise NotImplementedError("bf16-mixed with an adapter attached: LoRA on fp32 master weights is not built")
+            mx = self._mixed = mixed.MixedState(flat)   # (raises on a model that is not bf16)
+            self._opt = {"m": mx.m, "v": mx.v, "sumsq": mx.sumsq, "partial": mx.partial, "coef": mx.coef, "norm": mx.norm}
+            return self._opt
         self._opt = {
             "m": torch.zeros_like(flat), "v": torch.zeros_like(flat),
             "sumsq": torch.zeros(1, dtype=torch.float32, device=flat.device),
@@ -231,7 +247,8 @@ class TrainMIDIModel(MIDIModel):
         if self._reducer is not None:
             self._reducer.finish()
         o = self._opt
-        g = self.grad_buffer()
+        mx = self._mixed
+        g = self.grad_buffer() if mx is None else mx.g32
         if self.gradient_clip_val is not None and self.gradient_clip_val > 0:
             ops.sumsq(g, o["partial"], o["sumsq"], False)
             ops.clip_coef(o["sumsq"], float(self.gradient_clip_val), o["coef"], o["norm"])
@@ -244,10 +261,13 @@ class TrainMIDIModel(MIDIModel):
         bc1, bc2 = 1.0 - self.betas[0] ** step, 1.0 - self.betas[1] ** step
         nm = self._n_mat
         flat = self._flat
-        ops.adamw(flat[:nm], g[:nm], o["m"][:nm], o["v"][:nm], lr, self.betas[0], self.betas[1], self.eps,
-                  self.weight_decay, bc1, bc2, coef)
-        ops.adamw(flat[nm:], g[nm:], o["m"][nm:], o["v"][nm:], lr, self.betas[0], self.betas[1], self.eps, 0.0,
-                  bc1, bc2, coef)
+        if mx is not None:
+            mx.step(nm, lr, self.betas, self.eps, self.weight_decay, bc1, bc2, coef)
+        else:
+            ops.adamw(flat[:nm], g[:nm], o["m"][:nm], o["v"][:nm], lr, self.betas[0], self.betas[1], self.eps,
+                      self.weight_decay, bc1, bc2, coef)
+            ops.adamw(flat[nm:], g[nm:], o["m"][nm:], o["v"][nm:], lr, self.betas[0], self.betas[1], self.eps, 0.0,
+                      bc1, bc2, coef)
         self.weights_written()  # (raw-pointer write: data derived from the weights -- MIDIModel.folded_weights -- is stale now)
         self.global_step += 1
         self._micro = 0
@@ -292,7 +312,8 @@ class TrainMIDIModel(MIDIModel):
         group = dict(lr=lr_now, initial_lr=self.lr, betas=self.betas, eps=self.eps, amsgrad=False, maximize=False, foreach=None,
                      capturable=False, differentiable=False, fused=None)
         out = {
-            "state_dict": {k: t.detach().cpu().clone() for k, t in self.state_dict().items()},
+            "state_dict": ({k: t.detach().cpu().clone() for k, t in self.state_dict().items()} if self._mixed is None
+                           else {k: t.cpu() for k, t in self.master_state_dict().items()}),
             "global_step": int(self.global_step), "epoch": 0,
             "optimizer_states": [{"state": state, "param_groups": [
                 dict(group, weight_decay=self.weight_decay, params=list(range(n_decay))),
@@ -309,8 +330,23 @@ class TrainMIDIModel(MIDIModel):
             "hyper_parameters": dict(lr=self.lr, weight_decay=self.weight_decay, warmup=self.warmup, max_step=self.max_step),
             "mh_micro": int(self._micro),
         }
-        if self._micro > 0 and self._flat_grad is not None:
+        if self._mixed is not None and self._micro > 0:
+            out["mh_grad"] = self._mixed.g32.detach().cpu().clone()   # the fp32 accumulator of the open window
+        elif self._micro > 0 and self._flat_grad is not None:
             out["mh_grad"] = self._flat_grad.detach().cpu().clone()
+        return out
+
+    def master_state_dict(self) -> dict:
+        """bf16-mixed: the fp32 master weights by parameter name (what a Lightning ``bf16-mixed`` checkpoint's ``state_dict``
+        holds), in ``state_dict()`` order.  ``state_dict()`` itself stays the bf16 working copy."""
+        if self._mixed is None:
+            if self.precision != mixed.PRECISION_MIXED:
+                raise RuntimeError("master_state_dict: only a precision='bf16-mixed' model keeps fp32 master weights")
+            self.configure_optimizers()
+        out = {}
+        for k, t in self.state_dict().items():
+            off, cnt, _ = self._offsets[k]
+            out[k] = self._mixed.master[off:off + cnt].detach().clone().view(t.shape)
         return out
 
     def save_training_state(self, path: str) -> None:
@@ -336,6 +372,8 @@ class TrainMIDIModel(MIDIModel):
                 state = torch.load(state, map_location="cpu", weights_only=False)
         if "optimizer_states" not in state or "state_dict" not in state:
             raise RuntimeError("load_training_state: not a training checkpoint (needs state_dict + optimizer_states)")
+        if self.precision == mixed.PRECISION_MIXED and self._opt is None:
+            self.configure_optimizers()   # (first: load_state_dict then fills the fp32 master from the file directly)
         self.load_checkpoint_state(state)
         if self._opt is None:
             self.configure_optimizers()
@@ -377,7 +415,9 @@ class TrainMIDIModel(MIDIModel):
             raise RuntimeError(f"load_training_state: parameters disagree on the step count {sorted(steps)} (the fused AdamW keeps one)")
         self.global_step = int(state.get("global_step", steps.pop() if steps else 0))
         self._micro = int(state.get("mh_micro", 0))
-        if "mh_grad" in state:
+        if "mh_grad" in state and self._mixed is not None:
+            self._mixed.g32.copy_(state["mh_grad"].to(self._flat.device, torch.float32))
+        elif "mh_grad" in state:
             self.grad_buffer().copy_(state["mh_grad"].to(self._flat.device, self._flat.dtype))
         elif self._micro > 0:
             raise RuntimeError("load_training_state: the checkpoint was taken inside an accumulation window but holds no gradient")
@@ -395,6 +435,28 @@ class TrainMIDIModel(MIDIModel):
                 setattr(self, k, hp[k])
         return self
 
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        """nn.Module.load_state_dict; in bf16-mixed with the optimiser configured the tensors also go into the fp32 master AS THEY
+        ARE (fp32 values keep every bit: no bf16 round trip; a bf16 checkpoint upcasts) and the bf16 working copy is re-derived
+        from the master"""
+        res = super().load_state_dict(state_dict, strict=strict, assign=assign)
+        mx = getattr(self, "_mixed", None)
+        if mx is not None:
+            for name, t in state_dict.items():
+                if name in self._offsets:
+                    off, cnt, _ = self._offsets[name]
+                    mx.master[off:off + cnt].copy_(t.detach().reshape(-1).to(device=mx.master.device, dtype=torch.float32))
+            mx.derive_working_copy()
+            self.weights_written()
+        return res
+
+    def _apply(self, fn, recurse=True):
+        if getattr(self, "_mixed", None) is not None:
+            raise RuntimeError("bf16-mixed: the model cannot be moved or cast (.to() / .float() / .cuda()) after "
+                               "configure_optimizers(): the fp32 master weights are tied to the current bf16 parameter buffer and "
+                               "would be orphaned; move the model first, then configure the optimiser")
+        return super()._apply(fn, recurse)
+
     # ------------------------------------------------------------------------------------- LoRA
     def add_adapter(self, lora_config=None, **kwargs):
         """train.py:439-449: ``model.requires_grad_(False); model.add_adapter(LoraConfig(r=64, lora_alpha=128,
@@ -402,6 +464,9 @@ class TrainMIDIModel(MIDIModel):
         LoraConfig), a dict, or keyword arguments.  From here on training_step / optimizer_step update the adapters only;
         the base weights stay as loaded (lora.py)."""
         from .lora import DEFAULT_TARGETS, LoraAdapter
+        if self.precision == mixed.PRECISION_MIXED:
+            raise NotImplementedError("add_adapter with precision='bf16-mixed': LoRA on fp32 master weights is not built; "
+                                      "train adapters with precision=None (bf16-true)")
         self._require_gpu()
         cfg = dict(r=64, lora_alpha=128, target_modules=DEFAULT_TARGETS, lora_dropout=0.0)
         src = lora_config if isinstance(lora_config, dict) else (
@@ -501,6 +566,8 @@ class TrainMIDIModel(MIDIModel):
     def zero_grad(self, set_to_none: bool = False):
         if self._flat_grad is not None:
             self._flat_grad.zero_()
+        if self._mixed is not None:
+            self._mixed.g32.zero_()
         self._micro = 0
 
     # --------------------------------------------------------------------------------- fused step
@@ -560,7 +627,11 @@ class TrainMIDIModel(MIDIModel):
         row_loss = torch.empty(R, dtype=torch.float32, device=dev)
         argmax = torch.empty(R, dtype=torch.long, device=dev) if want_acc else None
         lm_w = self.lm_head.weight.data
-        accumulate = backward and self._micro > 0
+        if backward and self.precision == mixed.PRECISION_MIXED and self._mixed is None:
+            self.configure_optimizers()
+        # bf16-mixed: every micro-batch's gradient is computed into the bf16 buffer as a first micro-batch and folded into the
+        # fp32 accumulator range by range (_announce): the window's sum is taken in fp32
+        accumulate = backward and self._micro > 0 and self._mixed is None
         if backward:
             self.grad_buffer()
             dh = torch.empty((R, D), dtype=dty, device=dev)
@@ -658,13 +729,18 @@ class TrainMIDIModel(MIDIModel):
         if (self._micro + 1) % max(1, self.accumulate_grad_batches) != 0:
             return None
         r = self._reducer
-        if r is None or r.flat is not self._flat_grad or r.comm is not self.comm or r.force != self.force_reduce:
-            self._reducer = GradReducer(self._flat_grad, self.process_group, self.bucket_mb << 20, comm=self.comm,
+        buf = self._flat_grad if self._mixed is None else self._mixed.g32   # (bf16-mixed: 4 bytes per parameter go out)
+        if r is None or r.flat is not buf or r.comm is not self.comm or r.force != self.force_reduce:
+            self._reducer = GradReducer(buf, self.process_group, self.bucket_mb << 20, comm=self.comm,
                                         force=self.force_reduce)
         return self._reducer
 
-    @staticmethod
-    def _announce(red, lo: int, hi: int):
+    def _announce(self, red, lo: int, hi: int):
+        """flat gradient range [lo, hi) of this micro-batch is final.  bf16-mixed: fold it into the fp32 accumulator first (the
+        first micro-batch of a window overwrites, later ones add; the embedding tables come through their bf16 cast like every
+        other range), so that on the closing micro-batch the range the reducer ships is the fp32 one, still behind the backward"""
+        if self._mixed is not None:
+            self._mixed.fold(self._flat_grad, lo, hi, self._micro > 0)
         if red is not None:
             red.ready(lo, hi)
 
@@ -703,9 +779,15 @@ class TrainMIDIModel(MIDIModel):
     def broadcast_parameters(self, src: int = 0):
         """DDP constructor behaviour: rank `src`'s weights everywhere (one flat broadcast)."""
         import torch.distributed as dist
+        if self.precision == mixed.PRECISION_MIXED and self._mixed is None:
+            self.configure_optimizers()
+        # bf16-mixed: the master travels and the bf16 working copy is re-derived from it, so ranks agree bit for bit in both
+        buf = self._flat if self._mixed is None else self._mixed.master
         if self.comm is not None:
             if self.comm.world > 1 or self.force_reduce:
-                self.comm.broadcast_(self._flat, root=src)
+                self.comm.broadcast_(buf, root=src)
         elif dist.is_available() and dist.is_initialized() and dist.get_world_size(self.process_group) > 1:
-            dist.broadcast(self._flat, src=src, group=self.process_group)
+            dist.broadcast(buf, src=src, group=self.process_group)
+        if self._mixed is not None:
+            self._mixed.derive_working_copy()
         self.weights_written()
