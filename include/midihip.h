@@ -337,6 +337,28 @@ int mh_attn_decode(const void* qkv, const void* kcache, const void* vcache, void
 int mh_attn_decode_append(const void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache, void* o,
                           int64_t B, int H, int hd, int64_t Lmax, int64_t pos, float scale, const int32_t* pos_dev,
                           int dtype, void* stream);
+/* Decode over a prompt that every row of the batch shares (MIDIModel.generate(share_prompt=True)); head_dim 64 only.
+ * The prompt's K/V are cached once, kpre / vpre [H, Pmax, hd] (rows [0, pre_len) valid); each row keeps only its own suffix,
+ * ksuf / vsuf [B, H, Lsuf, hd].  qkv [B, 3*H*hd] holds the UNROTATED q,k,v of absolute position `pos` and is left untouched.
+ *   mh_attn_prefix_partial: one workgroup per (head, chunk of MH_ATTN_PREFIX_CHUNK prefix keys) rotates the B query rows at
+ *     `pos` (as mh_kv_append does), reads the chunk's K/V once and leaves per (b, h, chunk) an unnormalised fp32 acc[hd] with
+ *     its running maximum m and sum l in ws: acc [B, H, nch, hd] followed by (m, l) [B, H, nch, 2], nch = ceil(Pmax / chunk),
+ *     66 * B * H * nch floats.  Chunks at or past ceil(pre_len / chunk) are not written.  The grid depends on Pmax only.
+ *   mh_attn_decode_append_shared: mh_attn_decode_append over the suffix cache -- the rotated k row and the v row go to suffix
+ *     row pos - pre_len, attention covers suffix rows [0, pos - pre_len] -- then the row's ceil(pre_len / chunk) partials are
+ *     merged in chunk order before the division by l.
+ * pre_len_dev / pos_dev (optional, device int32): when non-null the kernels read the value from there (graph replay) and the
+ * host value is ignored.  Host values are validated: 1 <= pre_len <= Pmax, pos >= pre_len, pos - pre_len < Lsuf.
+ * mh_attn_prefix_chunk returns MH_ATTN_PREFIX_CHUNK.                                                                       */
+#define MH_ATTN_PREFIX_CHUNK 256
+int mh_attn_prefix_chunk(void);
+int mh_attn_prefix_partial(const void* qkv, const float* cos_t, const float* sin_t, const void* kpre, const void* vpre,
+                           float* ws, int64_t ws_floats, int64_t B, int H, int hd, int64_t Pmax, int64_t pre_len, int64_t pos,
+                           float scale, const int32_t* pre_len_dev, const int32_t* pos_dev, int dtype, void* stream);
+int mh_attn_decode_append_shared(const void* qkv, const float* cos_t, const float* sin_t, void* ksuf, void* vsuf,
+                                 const float* ws, int64_t ws_floats, void* o, int64_t B, int H, int hd, int64_t Lsuf,
+                                 int64_t Pmax, int64_t pre_len, int64_t pos, float scale, const int32_t* pre_len_dev,
+                                 const int32_t* pos_dev, int dtype, void* stream);
 /* A chunk of q_len > 1 new positions behind n cached ones (a cache-carrying forward, midi_model.py:137-150 with a non-empty
  * DynamicCache; TF:integrations/sdpa_attention.py:79-166): mh_kv_store_rows appends the chunk's rotated K and V at cache rows
  * [pos0, pos0 + S); mh_kv_gather_rows copies cache rows [0, n) into the K and V columns of rows [b*Stot, b*Stot + n) of a fused

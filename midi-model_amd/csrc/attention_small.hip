@@ -542,16 +542,31 @@ __device__ inline float group_sum(float v) {
 // keeps an online-softmax state over its own subset of keys, merged at the end (groups, then waves).
 // APPEND: qkv holds the UNROTATED q,k,v of the new position; the block first rotates k and stores the k,v rows at index
 // len-1 of its (b,h) cache (what kv_append_kernel does), rotates q in registers, then attends over rows [0, len).
-template <typename T, int HD, bool APPEND>
+// SHARED (APPEND only; generate(share_prompt=True), attention_shared.hip): the cache holds only the row's own SUFFIX behind a
+// prompt of pre_len events that all rows share.  `len` - 1 (or *pos_dev) is still the ABSOLUTE position -- RoPE runs there -- the
+// new row goes to suffix row pos - pre_len, the key loop covers suffix rows [0, pos - pre_len], and before normalising the
+// block adds the ceil(pre_len / chunk) partials (acc[HD], m, l) that mh_attn_prefix_partial left for its (b, h), in chunk order.
+// The trailing arguments are read by SHARED instantiations only.
+template <typename T, int HD, bool APPEND, bool SHARED = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ qkv, T* kc, T* vc, T* __restrict__ o, int H,
                                                           int64_t Lmax, int64_t len, float scale,
                                                           const int32_t* __restrict__ pos_dev,
-                                                          const float* __restrict__ cos_t, const float* __restrict__ sin_t) {
+                                                          const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+                                                          const float* __restrict__ part = nullptr, int nch = 0, int chunk = 1,
+                                                          int pre_len = 0, const int32_t* __restrict__ pre_len_dev = nullptr,
+                                                          int64_t n_bh = 0) {
+  static_assert(!SHARED || APPEND, "the shared-prefix form appends");
   // every kernel argument fetched at entry in one batch (hipcc sinks each s_load into the block that first uses it otherwise:
   // a scalar-cache miss + wait per block on a kernel whose whole run is a few microseconds)
   asm volatile("" ::"s"(qkv), "s"(kc), "s"(vc), "s"(o), "s"(H), "s"(Lmax), "s"(len), "s"(scale));
   asm volatile("" ::"s"(pos_dev), "s"(cos_t), "s"(sin_t));
   if (pos_dev != nullptr) len = (int64_t)*pos_dev + 1;  // graph replay: attend to rows [0, pos]
+  int64_t rpos = len - 1;  // the position RoPE runs at
+  if constexpr (SHARED) {
+    if (pre_len_dev != nullptr) pre_len = *pre_len_dev;
+    len -= pre_len;  // suffix rows [0, pos - pre_len]
+    if (len < 1) len = 1;
+  }
   if (len > Lmax) len = Lmax;
   constexpr int N = Pack<T>::N;
   constexpr int LPK = HD / N;       // lanes per key row
@@ -573,9 +588,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
   if constexpr (APPEND) {
     constexpr int half = HD / 2;
     const int64_t pos = len - 1;
+    if constexpr (!SHARED) rpos = pos;
     if (threadIdx.x < half) {  // k row (rotated) and v row of the new position -> cache
       const int i = threadIdx.x;
-      const float c = rnd<T>(cos_t[pos * half + i]), sn = rnd<T>(sin_t[pos * half + i]);
+      const float c = rnd<T>(cos_t[rpos * half + i]), sn = rnd<T>(sin_t[rpos * half + i]);
       const float k1 = to_f(qrow[D + i]), k2 = to_f(qrow[D + i + half]);
       T* kd = kc + (bh * Lmax + pos) * HD;
       T* vd = vc + (bh * Lmax + pos) * HD;
@@ -595,7 +611,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
 #pragma unroll
     for (int e = 0; e < N; ++e) {
       const int i = (base + e) % half;
-      const float c = rnd<T>(cos_t[pos * half + i]), sn = rnd<T>(sin_t[pos * half + i]);
+      const float c = rnd<T>(cos_t[rpos * half + i]), sn = rnd<T>(sin_t[rpos * half + i]);
       const float r = (base < half) ? qv.get(e) * c - qp.get(e) * sn : qv.get(e) * c + qp.get(e) * sn;
       q[e] = rnd<T>(r) * scale;
     }
@@ -706,13 +722,30 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
   }
   __syncthreads();
   if (threadIdx.x < HD) {
-    const float gm = fmaxf(fmaxf(sh_m[0], sh_m[1]), fmaxf(sh_m[2], sh_m[3]));
+    float gm = fmaxf(fmaxf(sh_m[0], sh_m[1]), fmaxf(sh_m[2], sh_m[3]));
+    const float* pacc = nullptr;
+    const float* pml = nullptr;
+    int np = 0;
+    if constexpr (SHARED) {  // the prompt's partials of this (b, h): acc [n_bh, nch, HD] then (m, l) [n_bh, nch, 2]
+      np = (pre_len + chunk - 1) / chunk;
+      np = np < nch ? np : nch;
+      pacc = part + bh * nch * HD;
+      pml = part + n_bh * nch * HD + bh * nch * 2;
+      for (int c = 0; c < np; ++c) gm = fmaxf(gm, pml[2 * c]);
+    }
     float num = 0.f, den = 0.f;
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
       const float f = (sh_m[w] == -INFINITY) ? 0.f : __expf(sh_m[w] - gm);
       num += sh_o[w][threadIdx.x] * f;
       den += sh_l[w] * f;
+    }
+    if constexpr (SHARED) {
+      for (int c = 0; c < np; ++c) {
+        const float f = __expf(pml[2 * c] - gm);
+        num += pacc[c * HD + threadIdx.x] * f;
+        den += pml[2 * c + 1] * f;
+      }
     }
     o[b * D + (int64_t)h * HD + threadIdx.x] = from_f<T>(num / den);
   }
@@ -760,6 +793,40 @@ extern "C" int mh_attn_decode_append(const void* qkv, const float* cos_t, const 
                                      const int32_t* pos_dev, int dtype, void* stream) {
   MH_REQUIRE(cos_t != nullptr && sin_t != nullptr, "attn_decode_append: needs the rope tables");
   return attn_decode_launch(qkv, cos_t, sin_t, kcache, vcache, o, B, H, hd, Lmax, pos + 1, scale, pos_dev, dtype, stream);
+}
+
+// The suffix half of decode attention over a shared prompt (attention_shared.hip holds the prefix half and the layout of `ws`).
+extern "C" int mh_attn_decode_append_shared(const void* qkv, const float* cos_t, const float* sin_t, void* ksuf, void* vsuf,
+                                            const float* ws, int64_t ws_floats, void* o, int64_t B, int H, int hd, int64_t Lsuf,
+                                            int64_t Pmax, int64_t pre_len, int64_t pos, float scale,
+                                            const int32_t* pre_len_dev, const int32_t* pos_dev, int dtype, void* stream) {
+  MH_REQUIRE(hd == 64, "attn_decode_append_shared: head_dim %d unsupported (64)", hd);
+  MH_REQUIRE(dtype == MH_BF16 || dtype == MH_F32, "attn_decode_append_shared: bad dtype %d", dtype);
+  MH_REQUIRE(qkv != nullptr && cos_t != nullptr && sin_t != nullptr && ksuf != nullptr && vsuf != nullptr && ws != nullptr &&
+                 o != nullptr, "attn_decode_append_shared: null buffer (the rope tables are needed: qkv arrives unrotated)");
+  MH_REQUIRE(B > 0 && H > 0 && Lsuf > 0 && Lsuf < (1 << 24) && Pmax > 0 && Pmax < (1 << 24),
+             "attn_decode_append_shared: bad args B=%ld H=%d Lsuf=%ld Pmax=%ld", (long)B, H, (long)Lsuf, (long)Pmax);
+  MH_REQUIRE(pre_len_dev != nullptr || (pre_len >= 1 && pre_len <= Pmax), "attn_decode_append_shared: bad args pre_len=%ld Pmax=%ld",
+             (long)pre_len, (long)Pmax);
+  MH_REQUIRE(pos_dev != nullptr || pos >= 0, "attn_decode_append_shared: bad args pos=%ld", (long)pos);
+  MH_REQUIRE(pre_len_dev != nullptr || pos_dev != nullptr || (pos >= pre_len && pos - pre_len < Lsuf),
+             "attn_decode_append_shared: bad args pos=%ld pre_len=%ld Lsuf=%ld (suffix row pos - pre_len must lie in [0, Lsuf))",
+             (long)pos, (long)pre_len, (long)Lsuf);
+  const int nch = (int)((Pmax + MH_ATTN_PREFIX_CHUNK - 1) / MH_ATTN_PREFIX_CHUNK);
+  MH_REQUIRE(ws_floats >= B * H * nch * 66, "attn_decode_append_shared: workspace of %ld floats, %ld needed", (long)ws_floats,
+             (long)(B * H * nch * 66));
+  hipStream_t st = (hipStream_t)stream;
+  const int grid = (int)(B * H);
+  if (dtype == MH_BF16)
+    attn_decode_kernel<bf16, 64, true, true><<<grid, 256, 0, st>>>((const bf16*)qkv, (bf16*)ksuf, (bf16*)vsuf, (bf16*)o, H, Lsuf,
+                                                                   pos + 1, scale, pos_dev, cos_t, sin_t, ws, nch,
+                                                                   MH_ATTN_PREFIX_CHUNK, (int)pre_len, pre_len_dev, B * H);
+  else
+    attn_decode_kernel<float, 64, true, true><<<grid, 256, 0, st>>>((const float*)qkv, (float*)ksuf, (float*)vsuf, (float*)o, H,
+                                                                    Lsuf, pos + 1, scale, pos_dev, cos_t, sin_t, ws, nch,
+                                                                    MH_ATTN_PREFIX_CHUNK, (int)pre_len, pre_len_dev, B * H);
+  MH_LAUNCH_CHECK();
+  return MH_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -23,6 +23,11 @@ The graphs are hipGraphs captured through torch.cuda.CUDAGraph from the same Pyt
 (``engine.stack_decode``), so there is one implementation of the step.  A session owns every buffer the graphs touch and
 is keyed by (parameter buffer, batch, capacity, temperature, top_p, top_k); ``MIDIModel`` keeps a pool of them and hands one to each
 ``generate`` call, so concurrent generators on one model (app.py:496) never share scratch.
+
+``shared_capacity`` > 0 (generate(share_prompt=True), shared.py): the B rows continue ONE prompt.  ``kvp`` (one sequence,
+shared_capacity rows) holds the prompt's K/V, ``kv1`` only the generated suffix, a device int32 ``pre_len`` sits beside ``pos``,
+and the net step's attention is the two launches of shared.py.  The captured graph reads ``pos`` and ``pre_len`` from device
+memory and its launch geometry depends on the capacities only, so one session serves every prompt length <= shared_capacity.
 """
 from __future__ import annotations
 
@@ -53,18 +58,25 @@ def graphs_enabled(device: torch.device) -> bool:
 
 
 class DecodeSession:
-    def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int):
+    def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int, shared_capacity: int = 0):
         tok = model.tokenizer
         self.model, self.B, self.cap, self.temp = model, B, capacity, float(temp)
         self.top_p, self.top_k = float(top_p), int(top_k)
-        self.key = self.make_key(model, B, capacity, temp, top_p, top_k)
+        self.shared_capacity = int(shared_capacity)
+        self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity)
         dev, dt = model.device, model.dtype
         self.T, self.V, self.Vp = tok.max_token_seq, tok.vocab_size, model.vocab_padded
         spec, tspec = model._specs["net"], model._specs["net_token"]
-        self.kv1 = KVState(spec, B, capacity, model._flat)
+        self.kv1 = KVState(spec, B, capacity, model._flat)  # (shared: the generated suffix only)
         self.kv2 = KVState(tspec, B, self.T, model._flat)
+        self.kvp = self.pre_len = self.ws = None
+        if self.shared_capacity > 0:
+            from . import shared
+            self.kvp = KVState(spec, 1, self.shared_capacity, model._flat)  # the prompt, once
+            self.pre_len = torch.zeros(1, dtype=torch.int32, device=dev)      # its length (device side, beside pos)
+            self.ws = torch.empty(shared.workspace_floats(B, spec.H, self.shared_capacity), dtype=torch.float32, device=dev)
         # rope tables private to the session: a captured graph keeps their addresses
-        self.rope1 = RopeTable(spec.hd, spec.theta, dev, capacity)
+        self.rope1 = RopeTable(spec.hd, spec.theta, dev, capacity + self.shared_capacity)
         self.rope2 = RopeTable(tspec.hd, tspec.theta, dev, self.T)
         first, lo, hi, _ = model._grammar()
         self.first_mask = first.clone()           # generate() overwrites it (ban_eos, disable_patch/control_change)
@@ -111,8 +123,9 @@ class DecodeSession:
             self._capture()
 
     @staticmethod
-    def make_key(model, B, capacity, temp, top_p, top_k):
-        return (model._flat.data_ptr(), model._flat.dtype, B, capacity, float(temp), float(top_p), int(top_k))
+    def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0):
+        key = (model._flat.data_ptr(), model._flat.dtype, B, capacity, float(temp), float(top_p), int(top_k))
+        return key + (("shared", int(shared_capacity)),) if shared_capacity else key
 
     def refresh(self) -> None:
         """Re-derive the folded weights (norm weight x projection) IN PLACE from the live parameters.  The training
@@ -133,7 +146,12 @@ class DecodeSession:
         spec = m._specs["net"]
         e = torch.empty((self.B, spec.D), dtype=m.dtype, device=m.device)
         ops.embed_sum_fwd(self.seq, m._W["net"].embed, e)  # the event sampled last
-        engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, pos_dev=self.pos, folded=self.fold1, out=self.hidden)
+        sh = None
+        if self.kvp is not None:
+            from .shared import SharedPrefix
+            sh = SharedPrefix(self.kvp, self.pre_len, self.ws)
+        engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, pos_dev=self.pos, folded=self.fold1, out=self.hidden,
+                            shared=sh)
         self.pos.add_(1)
 
     def _noise_body(self, generator=None):
@@ -247,12 +265,29 @@ class DecodeSession:
         self.kv1.len = 0
         self.kv2.len = 0
         self.pos.zero_()
+        if self.kvp is not None:
+            self.kvp.len = 0
+            self.pre_len.zero_()
 
     def prefill(self, tokens: torch.Tensor) -> None:
-        """tokens [B, S, T]: causal forward over the prompt from an empty cache; leaves hidden = last position."""
+        """tokens [B, S, T]: causal forward over the prompt from an empty cache; leaves hidden = last position.
+        A shared session runs ROW 0 alone (the caller has checked that the rows are equal) into ``kvp`` and hands its last hidden
+        row to all B rows; the suffix cache starts empty."""
         m = self.model
         spec = m._specs["net"]
         B, S, T = tokens.shape
+        if self.kvp is not None:
+            if S > self.shared_capacity:
+                raise ValueError(f"prompt of {S} events in a session whose shared capacity is {self.shared_capacity}")
+            e = torch.empty((S, spec.D), dtype=m.dtype, device=m.device)
+            ops.embed_sum_fwd(tokens[0].contiguous().view(S, T), m._W["net"].embed, e)
+            self.kvp.len = 0
+            self.kv1.len = 0
+            y = engine.stack_prefill(spec, m._W["net"], e, 1, S, self.rope1, self.kvp, folded=self.fold1)
+            self.hidden.copy_(y[S - 1:S].expand(self.B, -1))
+            self.pre_len.fill_(S)
+            self.pos.fill_(S)
+            return
         e = torch.empty((B * S, spec.D), dtype=m.dtype, device=m.device)
         ops.embed_sum_fwd(tokens.contiguous().view(B * S, T), m._W["net"].embed, e)
         self.kv1.len = 0

@@ -534,7 +534,7 @@ class _FoldList(list):
 
 
 def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTable, kv: KVState, pos_dev=None,
-                 folded=None, final_norm: bool = True, x_ids=None, out: Optional[torch.Tensor] = None):
+                 folded=None, final_norm: bool = True, x_ids=None, out: Optional[torch.Tensor] = None, shared=None):
     """x [B, D]: one new position per sequence at index kv.len (q_len == 1 => no causal mask,
     TF:integrations/sdpa_attention.py:120).
 
@@ -545,14 +545,32 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
     q|k|v and gate|up projections); otherwise the general GEMM is used (9 launches + split-K reductions).
     ``final_norm=False`` returns the residual stream before the stack's last RMSNorm (decode.py folds it into lm_head).
     ``x_ids`` (folded form only): ``x`` is an embedding table and row b of the input is x[x_ids[b]] -- the lookup happens
-    inside the first layer's projections."""
+    inside the first layer's projections.
+    ``shared`` = (kvp, pre_len_dev, workspace) (shared.SharedPrefix; event level, head_dim 64): the B rows continue ONE prompt
+    whose K/V sit once in ``kvp`` (a KVState of one sequence, kvp.len rows) and ``kv`` holds only each row's suffix.  The
+    position is kvp.len + kv.len (RoPE runs there), the new K/V row goes to suffix row kv.len, and in every form of the layer the
+    attention step is the two launches of shared.py (attn_prefix_partial, attn_decode_append_shared: +1 launch per layer against
+    the fused forms).  pre_len_dev goes with pos_dev: device int32[1] values a captured graph reads."""
     _check_heads(spec)
     B, D = (x_ids.shape[0], x.shape[1]) if x_ids is not None else x.shape
     assert x_ids is None or folded is not None
     H, I, hd = spec.H, spec.I, spec.hd
     pos = kv.len if pos_dev is None else 0
+    attend_shared = None
+    if shared is not None:
+        from . import shared as sp
+        kvp, pre_len_dev, ws = shared
+        assert spec.kind == "event" and kvp.B == 1 and (pre_len_dev is None) == (pos_dev is None)
+        pre, row = (kvp.len, kv.len) if pos_dev is None else (0, 0)
+        pos = pre + row
+
+        def attend_shared(qkv, o, li):
+            sp.attn_prefix_partial(qkv, rope.cos, rope.sin, kvp.k[li], kvp.v[li], ws, B, H, hd, kvp.cap, pre, pos, spec.scale,
+                                   pre_len_dev, pos_dev)
+            sp.attn_decode_append_shared(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], ws, o, B, H, hd, kv.cap, kvp.cap, pre, pos,
+                                         spec.scale, pre_len_dev, pos_dev)
     if pos_dev is None:
-        kv.reserve(pos + 1)
+        kv.reserve((pos if shared is None else kv.len) + 1)
         rope.ensure(pos + 1)
     fused = (x_ids is not None) or (ops.skinny_ok(x, D) and ops.skinny_ok(x, I))
     for li, lw in enumerate(W.layers):
@@ -562,7 +580,10 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
             qkv = _empty((B, 3 * D), x)
             ops.gemm_skinny(x, wqkv_n, qkv, norm_eps=spec.eps, row_ids=ids)
             o = _empty((B, D), x)
-            ops.attn_decode_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos, spec.scale, pos_dev)
+            if attend_shared is not None:
+                attend_shared(qkv, o, li)
+            else:
+                ops.attn_decode_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos, spec.scale, pos_dev)
             x2 = _empty((B, D), x)
             ops.gemm_skinny(o, lw.wo, x2, res=x, res_ids=ids)
             a = _empty((B, I), x)
@@ -577,7 +598,10 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
             qkv = _empty((B, 3 * D), x)
             ops.gemm_skinny(h1, lw.wqkv, qkv)
             o = h1
-            ops.attn_decode_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos, spec.scale, pos_dev)
+            if attend_shared is not None:
+                attend_shared(qkv, o, li)
+            else:
+                ops.attn_decode_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos, spec.scale, pos_dev)
             x2 = _empty((B, D), x)
             ops.gemm_skinny(o, lw.wo, x2, res=x)
             h2 = o
@@ -592,9 +616,12 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
         ops.rmsnorm_fwd(x, lw.n1, h1, None, spec.eps)
         qkv = _empty((B, 3 * D), x)
         ops.gemm_nt(h1, lw.wqkv, qkv)
-        ops.kv_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], B, H, hd, kv.cap, pos, pos_dev)
         o = h1
-        ops.attn_decode(qkv, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos + 1, spec.scale, pos_dev)
+        if attend_shared is not None:
+            attend_shared(qkv, o, li)
+        else:
+            ops.kv_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], B, H, hd, kv.cap, pos, pos_dev)
+            ops.attn_decode(qkv, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos + 1, spec.scale, pos_dev)
         x2 = _empty((B, D), x)
         ops.gemm_nt(o, lw.wo, x2, beta=1.0, res=x)
         h2 = o
@@ -607,7 +634,7 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
         ops.gemm_nt(a, lw.wd, x3, beta=1.0, res=x2)
         x = x3
     if pos_dev is None:
-        kv.len = pos + 1
+        kv.len = (pos if shared is None else kv.len) + 1
     if not final_norm:
         return x
     y = out if out is not None else _empty((B, D), x)  # (`out`: the caller's buffer -- a decode session's `hidden` -- no copy)

@@ -451,7 +451,7 @@ class MIDIModel(nn.Module):
 
     def generate(self, prompt=None, batch_size=1, max_len=512, temp=1.0, top_p=0.98, top_k=20, generator=None,
                  ban_eos: bool = False, disable_patch_change: bool = False, disable_control_change: bool = False,
-                 disable_channels=None):
+                 disable_channels=None, share_prompt: bool = False):
         """midi_model.py:167-250 with the host-bound parts moved to the device: grammar masks come from
         per-event-id range tables (no Python loop over the batch), K/V live in preallocated buffers, every decode /
         sampling step is a replayed hipGraph (decode.py) and the only device->host traffic is ONE copy of the B sampled
@@ -460,22 +460,48 @@ class MIDIModel(nn.Module):
 
         Returns ``np.ndarray (B, <= max_len, 8) int64`` including the prompt.  Extras (ours): ``ban_eos`` removes EOS
         from the first-token mask (throughput runs); ``disable_patch_change`` / ``disable_control_change`` /
-        ``disable_channels`` are the mask options of the serving loop (app.py:27-31, 73-86)."""
+        ``disable_channels`` are the mask options of the serving loop (app.py:27-31, 73-86).
+
+        ``share_prompt=True`` (ours; what every caller of the reference does: B continuations of ONE prompt) takes a
+        ``(L, T')`` prompt, a ``(1, L, T')`` prompt or a ``(batch_size, L, T')`` prompt whose rows are all equal (checked on the
+        host; unequal rows raise ``ValueError`` naming the first row that differs).  The prompt is prefilled once instead of B
+        times, its K/V are cached once instead of B times, and every decoded event reads them once per head for all B rows
+        (shared.py).  With ``prompt=None`` there is nothing to share and the plain path runs.  Output shape, dtype,
+        prompt inclusion, ``max_len``, the break rule and the mask options are those of the plain path, and the same
+        ``[8, B, V]`` variates are drawn from ``generator`` in the same order, so a seeded generator is left in the same state.
+        The logits are summed in another order than on the plain path (the prompt's keys in chunks of 256, then the suffix), so
+        sampled ids may differ from the plain path's where two candidates are within rounding of each other: bit equality with
+        the plain path is NOT promised (two shared runs are bit-identical).
+        Crossover ((B, P) below which sharing is slower): NOT MEASURED at this commit -- ``tools/bench_shared_prompt.py`` is the
+        vehicle and no MI355X run of it exists yet; from bytes alone sharing adds 12 launches per event and saves
+        (B - 1) x P x 49,152 bytes of K/V reads, so expect it to lose at short prompts and small B.  Opt-in for that reason."""
+        shared = self._shares_prompt(prompt, share_prompt)
         inp = self._prompt_tensor(prompt, batch_size)
         parts = [inp.cpu().numpy()]
         for ev in self._generate_events(inp, batch_size, max_len, temp, top_p, top_k, generator, ban_eos,
-                                        disable_patch_change, disable_control_change, disable_channels):
+                                        disable_patch_change, disable_control_change, disable_channels, shared):
             parts.append(ev[:, None, :])
         return np.concatenate(parts, axis=1)
 
     def generate_stream(self, prompt=None, batch_size=1, max_len=512, temp=1.0, top_p=0.98, top_k=20,
-                        disable_patch_change=False, disable_control_change=False, disable_channels=None, generator=None):
+                        disable_patch_change=False, disable_control_change=False, disable_channels=None, generator=None,
+                        share_prompt: bool = False):
         """The serving loop of the reference (app.py:27-120, same arguments): a Python generator that yields every new
         event as ``np.ndarray (B, 8) int64`` as soon as it is sampled; the prompt is cropped to its last 4096 events
-        (app.py:53).  Same kernels and sessions as ``generate``."""
+        (app.py:53).  Same kernels and sessions as ``generate``; ``share_prompt`` as there (the crop comes first)."""
+        shared = self._shares_prompt(prompt, share_prompt)
         inp = self._prompt_tensor(prompt, batch_size)[:, -4096:]
         return self._generate_events(inp, batch_size, max_len, temp, top_p, top_k, generator, False,
-                                     disable_patch_change, disable_control_change, disable_channels)
+                                     disable_patch_change, disable_control_change, disable_channels, shared)
+
+    @staticmethod
+    def _shares_prompt(prompt, share_prompt: bool) -> bool:
+        """share_prompt=True with a prompt: its rows must be equal (host check, before any launch); without one: plain path"""
+        if not share_prompt or prompt is None:
+            return False
+        from .shared import check_equal_rows
+        check_equal_rows(prompt)
+        return True
 
     def _prompt_tensor(self, prompt, batch_size: int) -> torch.Tensor:
         """prompt handling of midi_model.py:171-188 (and app.py:35-52): None -> one BOS event per sequence"""
@@ -502,7 +528,7 @@ class MIDIModel(nn.Module):
         return torch.from_numpy(np.ascontiguousarray(prompt)).to(dtype=torch.long, device=dev)
 
     def _generate_events(self, inp, batch_size, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
-                         disable_control_change, disable_channels):
+                         disable_control_change, disable_channels, shared: bool = False):
         """generator over the new events ((B, 8) int64 numpy each); the session is returned to the pool when the
         generator finishes or is closed"""
         tok = self.tokenizer
@@ -530,7 +556,10 @@ class MIDIModel(nn.Module):
         if len(chans) >= n_chan:
             raise ValueError("generate: disable_channels bans every channel id: no legal token is left at the channel position")
         with torch.inference_mode():
-            ses = self._checkout_session(B, max(max_len, cur_len) + 1, float(temp), float(top_p), int(top_k))
+            if shared:  # the prompt in its own cache; the per-row cache holds the generated suffix only
+                ses = self._checkout_session(B, max_len - cur_len + 1, float(temp), float(top_p), int(top_k), shared_need=cur_len)
+            else:
+                ses = self._checkout_session(B, max(max_len, cur_len) + 1, float(temp), float(top_p), int(top_k))
         try:
             with torch.inference_mode():
                 ses.first_mask.copy_(self._grammar()[0])
@@ -567,12 +596,19 @@ class MIDIModel(nn.Module):
             self._return_session(ses)
 
     # decode sessions: buffers + captured graphs, one per concurrent generate() call (decode.py)
-    def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int):
+    def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int, shared_need: int = 0):
+        """``shared_need`` > 0: a shared-prompt session whose prompt cache holds shared_need events (capacities by the same
+        doubling rule from 256, so one captured session serves a range of prompt and suffix lengths)"""
         from .decode import DecodeSession
         cap = 256
         while cap < need:
             cap *= 2
-        key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k)
+        scap = 0
+        if shared_need > 0:
+            scap = 256
+            while scap < shared_need:
+                scap *= 2
+        key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap)
         pool = self._sessions
         with pool.lock:
             found = None
@@ -585,7 +621,7 @@ class MIDIModel(nn.Module):
         if found is not None:
             found.refresh()  # weights may have been trained / merged since the session derived its folded copies
             return found
-        return DecodeSession(self, B, cap, temp, top_p, top_k)
+        return DecodeSession(self, B, cap, temp, top_p, top_k, scap)
 
     def _return_session(self, ses) -> None:
         with self._sessions.lock:
