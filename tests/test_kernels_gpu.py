@@ -91,6 +91,9 @@ def cmp(got, want, dtype, k=1.0, what=""):
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (256, 384, 256), (257, 200, 96), (1, 1024, 1024), (1000, 72, 8),
                                    (64, 3406, 256), (640, 1024, 4096)])
 def test_gemm_nt(ops, gemm_variant, dtype, M, N, K):
+    """workload shapes against the fp32 emulation.  The bf16 tolerance (2e-2 K / 256, absolute and relative) is wide enough for
+    a dropped K-step or a bf16 intermediate to pass, and the fp32 mode runs the 128x128 kernel, not the production one: the
+    bit-exact checks at the tile, K-loop and split-K edges are in test_gemm_gpu.py"""
     a, b = rnd((M, K), dtype, 1), rnd((N, K), dtype, 2)
     want = emu.gemm_nt(a, b, torch.empty((M, N), dtype=dtype))
     out = torch.full((M, N), float("nan"), dtype=dtype, device="cuda")
@@ -216,7 +219,9 @@ def test_gemm_main_loops_agree_bit_for_bit(ops):
 
 @pytest.mark.parametrize("M,I,K", [(256, 128, 64), (300, 640, 1024), (1000, 4096, 1024), (77, 1024, 264)])
 def test_gemm_swiglu(ops, main_loop, M, I, K):
-    """gate|up projection with the SwiGLU forward as its epilogue == mh_gemm_nt followed by mh_swiglu_fwd"""
+    """gate|up projection with the SwiGLU forward as its epilogue == mh_gemm_nt followed by mh_swiglu_fwd (both sides share
+    the main loop and the tile order: a fault there cancels, and only the loose comparison with the emulation remains; the
+    product itself is held to an exact reference in test_gemm_gpu.py)"""
     dt = torch.bfloat16
     x, w = rnd((M, K), dt, 64, 0.5), rnd((2 * I, K), dt, 65, 0.5)
     assert ops.swiglu_fused_ok(x.cuda(), I)
@@ -237,8 +242,9 @@ def test_gemm_swiglu(ops, main_loop, M, I, K):
 
 @pytest.mark.parametrize("B,S,H,K", [(1, 256, 4, 64), (2, 150, 2, 256), (3, 100, 16, 1024), (1, 77, 1, 264), (2, 2048, 16, 1024)])
 def test_gemm_rope(ops, main_loop, B, S, H, K):
-    """q|k|v projection with the rotary embedding as its epilogue == mh_gemm followed by mh_rope (bit for bit), and the
-    emulation within the bf16 bound"""
+    """q|k|v projection with the rotary embedding as its epilogue == mh_gemm followed by mh_rope (bit for bit; both sides
+    share the main loop), and the emulation ON THE KERNEL'S OWN PRODUCT within the bf16 tolerance; pos0 = 0 and S <= M only
+    (pos0 > 0, S = 1, S > M and the product against an exact reference: test_gemm_gpu.py)"""
     from midi_model_amd.engine import RopeTable
     dt = torch.bfloat16
     M, D = B * S, H * 64
