@@ -179,6 +179,18 @@ int mh_embed_scatter_bwd(const int64_t* tok, int64_t ldtok, int T, const void* d
  * seg_start[v+1])} dout[src_rows[i]*ld ...]; id `pad_id` is skipped.  n_occ = seg_start[V] = length of src_rows. */
 int mh_embed_segment_bwd(const int64_t* src_rows, const int64_t* seg_start, const void* dout, int64_t ld,
                          float* dtable_f32, int64_t V, int D, int64_t n_occ, int64_t pad_id, int dtype, void* stream);
+/* The per-vocabulary backward of the first token-level block (engine.tok_first_backward):
+ *   mh_embed_segment_sum     sum_f32[v * ldsum + c] += sum over i in [seg_start[v], seg_start[v+1]) of rows[src_rows[i] * ld + c],
+ *                            c < D, every id included (no pad exclusion); rows of any width D % 8 == 0, summed in slabs of 1024
+ *                            (bf16) columns that each run the 8-wave form of mh_embed_segment_bwd.
+ *   mh_embed_split_hi_lo     hi = round(s), lo = round(s - hi) in `dtype` (n elements, a multiple of 4).
+ *   mh_embed_table_norm_bwd  acc32[v, :] += T_v - e_v (rstd[v]^2 / D) rowdot(T_v, e_v), T_v = t_hi[v] + t_lo[v] in fp32, for every
+ *                            row v != pad_id of the [V, D] table e: mh_rmsnorm_bwd_folded applied after the sum over an id's rows. */
+int mh_embed_segment_sum(const int64_t* src_rows, const int64_t* seg_start, const void* rows, int64_t ld, float* sum_f32,
+                         int64_t ldsum, int64_t V, int D, int64_t n_occ, int dtype, void* stream);
+int mh_embed_split_hi_lo(const float* s, void* hi, void* lo, int64_t n, int dtype, void* stream);
+int mh_embed_table_norm_bwd(const void* t_hi, const void* t_lo, const void* e, const float* rstd, float* acc32, int64_t V, int D,
+                            int64_t pad_id, int dtype, void* stream);
 /* Index preparation of mh_embed_segment_bwd: a counting sort of the occurrences of the id matrix tok[n_rows, n_cols] (row
  * stride ldtok) by token id (replaces the reference's implicit scatter of nn.Embedding's backward, TF:models/llama/
  * modeling_llama.py:353; midi_model.py:126-131,143-145 are the two embeddings).  seg_start[v] (V + 1 entries) = occurrences
@@ -286,6 +298,18 @@ int mh_tokattn_bwd(const void* qkv, const void* dout, void* dqkv, int64_t N, int
 /* the same with row m = n * T + t of dqkv multiplied by rowscale[m] in the stores (the folded RMSNorm's d z) */
 int mh_tokattn_bwd_scaled(const void* qkv, const void* dout, void* dqkv, const float* rowscale, int64_t N, int T, int H, float scale,
                           const float* cos_t, const float* sin_t, int dtype, void* stream);
+/* The row-indirect octet forms (T = 8; the first token-level block of the folded training step, whose inputs at positions 1..7 are
+ * rows of the embedding table: engine.tok_first_forward / tok_first_backward).  zc [tab0 + V, 3*H*256] = the q|k|v projection of
+ * [hidden rows ; ... ; table rows from row tab0 on]; position 0 of sequence n reads row n, position p >= 1 reads row
+ * tab0 + ids[n * ldid + p - 1] (ids in [0, V); out-of-range values are clamped, not diagnosed).  o [N*8, H*256] and dz [N*8, 3*H*256]
+ * keep the layout of mh_tokattn_fwd / mh_tokattn_bwd and hold the same bits as those give on the materialised rows; with dz_hid
+ * (optional, [N, 3*H*256]) position 0's rows of dz go there and rows 8n of dz are left unwritten.  rowscale (optional, fp32) is
+ * indexed like the rows of zc. */
+int mh_tokattn_fwd_rows(const void* zc, const int64_t* ids, int64_t ldid, int64_t tab0, int64_t V, void* o, int64_t N, int H,
+                        float scale, const float* cos_t, const float* sin_t, int dtype, void* stream);
+int mh_tokattn_bwd_rows(const void* zc, const int64_t* ids, int64_t ldid, int64_t tab0, int64_t V, const void* dout, void* dz,
+                        void* dz_hid, const float* rowscale, int64_t N, int H, float scale, const float* cos_t, const float* sin_t,
+                        int dtype, void* stream);
 
 /* ---- SwiGLU (TF:models/llama/modeling_llama.py:174-176) -------------------------------------------------
  * gu[M,2I] = [gate | up];  a = silu(gate) * up;  dgu = [da*up*silu'(gate) | da*silu(gate)]            */

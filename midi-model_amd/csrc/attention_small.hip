@@ -106,10 +106,27 @@ __device__ inline void rope_row(float (&x)[4], const float* rope_c, const float*
 // every row of the (sequence, head) -- K, V, Q (and dO) -- is requested before the first one is used; the run-time form
 // branches per row and was a chain of 16 dependent HBM round trips per wave (r01_run20: 604 us forward, 1.3 ms backward
 // for 2.1 / 3.8 GB).
-template <typename T, int TN>
+// IND (TN = 8 only; the first block of the folded training forward, mh_tokattn_fwd_rows): the rows of a sequence are not
+// consecutive -- `qkv` is the projection of [hidden ; embedding table], position 0 of sequence n reads row n and position
+// p >= 1 reads row tab0 + ids[n * ldid + p - 1].  The 7 ids arrive in one load (lane p holds position p's), then all 24 rows
+// are requested as in the consecutive form; the arithmetic is the same instruction for instruction.
+struct TokRows {
+  const int64_t* ids;  // [N, ldid] token ids of positions 1..7 (columns 0..6)
+  int64_t ldid, tab0;  // row of table entry 0 in the projected buffer
+  int V;               // table rows (ids are clamped to [0, V) -- the caller has validated them)
+};
+template <int TN>
+__device__ inline int tok_row_lane(const TokRows& tr, int64_t n, int lane) {
+  int id = 0;
+  if (lane >= 1 && lane < TN) id = (int)tr.ids[n * tr.ldid + lane - 1];
+  return id < 0 ? 0 : (id >= tr.V ? tr.V - 1 : id);
+}
+
+template <typename T, int TN, bool IND = false>
 __global__ __launch_bounds__(256) void tokattn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ o, int64_t NH, int Tn,
                                                           int H, float scale, const float* __restrict__ cos_t,
-                                                          const float* __restrict__ sin_t) {
+                                                          const float* __restrict__ sin_t, TokRows tr = TokRows{}) {
+  static_assert(!IND || TN == TK, "row indirection: the octet form only");
   const int lane = threadIdx.x & 63;
   const int64_t D = (int64_t)H * 256, D3 = 3 * D;
   // RoPE on load (cos_t != nullptr): q, k come unrotated straight from the projection; position = token index
@@ -125,18 +142,28 @@ __global__ __launch_bounds__(256) void tokattn_fwd_kernel(const T* __restrict__ 
   for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < NH; w += (int64_t)gridDim.x * 4) {
     const int64_t n = w / H;
     const int h = (int)(w - n * H);
-    const T* base = qkv + n * Tn * D3 + (int64_t)h * 256;
+    const T* base = qkv + (IND ? 0 : n * Tn * D3) + (int64_t)h * 256;
     float k[TK][4], v[TK][4];
     RawRow<T> qraw[TN ? TN : 1];
     if constexpr (TN != 0) {
       RawRow<T> kraw[TN ? TN : 1], vraw[TN ? TN : 1];
+      int64_t roff[TN ? TN : 1];  // element offset of position t's row
+      if constexpr (IND) {
+        const int idl = tok_row_lane<TN>(tr, n, lane);
+        roff[0] = n * D3;
 #pragma unroll
-      for (int t = 0; t < TN; ++t) {
-        kraw[t] = ldraw<T>(base + t * D3 + D, lane);
-        vraw[t] = ldraw<T>(base + t * D3 + 2 * D, lane);
+        for (int t = 1; t < TN; ++t) roff[t] = (tr.tab0 + __builtin_amdgcn_readlane(idl, t)) * D3;
+      } else {
+#pragma unroll
+        for (int t = 0; t < TN; ++t) roff[t] = t * D3;
       }
 #pragma unroll
-      for (int t = 0; t < TN; ++t) qraw[t] = ldraw<T>(base + t * D3, lane);
+      for (int t = 0; t < TN; ++t) {
+        kraw[t] = ldraw<T>(base + roff[t] + D, lane);
+        vraw[t] = ldraw<T>(base + roff[t] + 2 * D, lane);
+      }
+#pragma unroll
+      for (int t = 0; t < TN; ++t) qraw[t] = ldraw<T>(base + roff[t], lane);
 #pragma unroll
       for (int t = 0; t < TN; ++t) {
         unpack(kraw[t], k[t]);
@@ -189,11 +216,15 @@ __global__ __launch_bounds__(256) void tokattn_fwd_kernel(const T* __restrict__ 
 
 // BR (r06): the 2 (i + 1) score / d-probability dot products of query row i are reduced four at a time (wave_sum4) instead of
 // one by one -- 20 batched reductions per (sequence, head) instead of 72 single ones.  Same values up to fp32 summation order.
-template <typename T, int TN, bool BR>
+// IND (mh_tokattn_bwd_rows): operand rows and row scales through the indirection of the forward's IND form; dqkv keeps its
+// [N * 8, 3D] rows, and position 0 of sequence n goes to row n of `dq_hid` instead when that is given.
+template <typename T, int TN, bool BR, bool IND = false>
 __global__ __launch_bounds__(256) void tokattn_bwd_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
                                                           T* __restrict__ dqkv, int64_t NH, int Tn, int H, float scale,
                                                           const float* __restrict__ cos_t, const float* __restrict__ sin_t,
-                                                          const float* __restrict__ rowscale /* != NULL: row m of dqkv times rowscale[m] */) {
+                                                          const float* __restrict__ rowscale /* != NULL: row m of dqkv times rowscale[m] */,
+                                                          TokRows tr = TokRows{}, T* __restrict__ dq_hid = nullptr) {
+  static_assert(!IND || TN == TK, "row indirection: the octet form only");
   const int lane = threadIdx.x & 63;
   const int64_t D = (int64_t)H * 256, D3 = 3 * D;
   // RoPE on load and its transpose on the way out (cos_t != nullptr): qkv is the unrotated projection output and dqkv
@@ -211,27 +242,40 @@ __global__ __launch_bounds__(256) void tokattn_bwd_kernel(const T* __restrict__ 
     const int64_t n = w / H;
     const int h = (int)(w - n * H);
     const int64_t off = (int64_t)h * 256;
-    const T* base = qkv + n * Tn * D3 + off;
+    const T* base = qkv + (IND ? 0 : n * Tn * D3) + off;
     T* ob = dqkv + n * Tn * D3 + off;
+    T* ob0 = (IND && dq_hid != nullptr) ? dq_hid + n * D3 + off : ob;  // where position 0's row goes
     float k[TK][4], v[TK][4], dk[TK][4], dv[TK][4];
     RawRow<T> qraw[TN ? TN : 1], doraw[TN ? TN : 1];
+    int idl = 0;
+    if constexpr (IND) idl = tok_row_lane<TN>(tr, n, lane);
     // (the sequence's <= 8 row scales in ONE load beside the operand rows -- lane t holds row t's; broadcast below by lane index:
     //  a scalar load per stored row sat on the critical path of this bandwidth-bound kernel, +12 % on the launch)
-    const float rs_lane = (rowscale != nullptr && lane < Tn) ? rowscale[n * Tn + lane] : 1.f;
+    const int64_t rs_row = IND ? (lane == 0 ? n : tr.tab0 + idl) : n * Tn + lane;
+    const float rs_lane = (rowscale != nullptr && lane < Tn) ? rowscale[rs_row] : 1.f;
 #pragma unroll
     for (int t = 0; t < TK; ++t)
 #pragma unroll
       for (int e = 0; e < 4; ++e) dk[t][e] = dv[t][e] = 0.f;
     if constexpr (TN != 0) {
       RawRow<T> kraw[TN ? TN : 1], vraw[TN ? TN : 1];
+      int64_t roff[TN ? TN : 1];  // element offset of position t's row
+      if constexpr (IND) {
+        roff[0] = n * D3;
 #pragma unroll
-      for (int t = 0; t < TN; ++t) {
-        kraw[t] = ldraw<T>(base + t * D3 + D, lane);
-        vraw[t] = ldraw<T>(base + t * D3 + 2 * D, lane);
+        for (int t = 1; t < TN; ++t) roff[t] = (tr.tab0 + __builtin_amdgcn_readlane(idl, t)) * D3;
+      } else {
+#pragma unroll
+        for (int t = 0; t < TN; ++t) roff[t] = t * D3;
       }
 #pragma unroll
       for (int t = 0; t < TN; ++t) {
-        qraw[t] = ldraw<T>(base + t * D3, lane);
+        kraw[t] = ldraw<T>(base + roff[t] + D, lane);
+        vraw[t] = ldraw<T>(base + roff[t] + 2 * D, lane);
+      }
+#pragma unroll
+      for (int t = 0; t < TN; ++t) {
+        qraw[t] = ldraw<T>(base + roff[t], lane);
         doraw[t] = ldraw<T>(dout + (n * Tn + t) * D + off, lane);
       }
 #pragma unroll
@@ -323,7 +367,7 @@ __global__ __launch_bounds__(256) void tokattn_bwd_kernel(const T* __restrict__ 
 #pragma unroll
         for (int e = 0; e < 4; ++e) dq[e] *= rsc;
       }
-      stp<T>(ob + i * D3, lane, dq);
+      stp<T>((i == 0 ? ob0 : ob + i * D3), lane, dq);
     }
 #pragma unroll
     for (int t = 0; t < TK; ++t) {
@@ -337,8 +381,9 @@ __global__ __launch_bounds__(256) void tokattn_bwd_kernel(const T* __restrict__ 
             dv[t][e] *= rsc;
           }
         }
-        stp<T>(ob + t * D3 + D, lane, dk[t]);
-        stp<T>(ob + t * D3 + 2 * D, lane, dv[t]);
+        T* orow = t == 0 ? ob0 : ob + t * D3;
+        stp<T>(orow + D, lane, dk[t]);
+        stp<T>(orow + 2 * D, lane, dv[t]);
       }
     }
   }
@@ -389,6 +434,45 @@ extern "C" int mh_tokattn_bwd_scaled(const void* qkv, const void* dout, void* dq
                                      float scale, const float* cos_t, const float* sin_t, int dtype, void* stream) {
   MH_REQUIRE(rowscale != nullptr, "tokattn_bwd_scaled: rowscale is NULL");
   return tokattn_bwd_any(qkv, dout, dqkv, rowscale, N, Tn, H, scale, cos_t, sin_t, dtype, stream);
+}
+
+// The row-indirect octet forms (see TokRows): zc = the q|k|v projection of [hidden (tab0 rows before the table) ; table (V rows)],
+// ids[n, p - 1] = the table row of position p >= 1 of sequence n.  o and dz keep the [N * 8, .] layout of the consecutive forms;
+// dz_hid (optional, [N, 3D]) receives position 0's rows of dz in their place; rowscale (optional) is indexed like zc's rows.
+static int tokattn_rows_check(const void* zc, const int64_t* ids, int64_t ldid, int64_t tab0, int64_t V, int64_t N, int H) {
+  MH_REQUIRE(zc != nullptr && ids != nullptr && ldid >= TK - 1 && tab0 >= N && V > 0 && V < (1ll << 31) && N > 0 && H >= 1,
+             "tokattn_rows: bad arguments N=%ld H=%d V=%ld tab0=%ld ldid=%ld", (long)N, H, (long)V, (long)tab0, (long)ldid);
+  return MH_OK;
+}
+extern "C" int mh_tokattn_fwd_rows(const void* zc, const int64_t* ids, int64_t ldid, int64_t tab0, int64_t V, void* o, int64_t N,
+                                   int H, float scale, const float* cos_t, const float* sin_t, int dtype, void* stream) {
+  if (int rc = tokattn_rows_check(zc, ids, ldid, tab0, V, N, H)) return rc;
+  const int64_t NH = N * H;
+  int64_t g = (NH + 3) / 4;
+  if (g > 32768) g = 32768;
+  const TokRows tr{ids, ldid, tab0, (int)V};
+  DISPATCH_T(dtype, (tokattn_fwd_kernel<T, TK, true><<<(int)g, 256, 0, (hipStream_t)stream>>>((const T*)zc, (T*)o, NH, TK, H, scale,
+                                                                                             cos_t, sin_t, tr)));
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+extern "C" int mh_tokattn_bwd_rows(const void* zc, const int64_t* ids, int64_t ldid, int64_t tab0, int64_t V, const void* dout,
+                                   void* dz, void* dz_hid, const float* rowscale, int64_t N, int H, float scale,
+                                   const float* cos_t, const float* sin_t, int dtype, void* stream) {
+  if (int rc = tokattn_rows_check(zc, ids, ldid, tab0, V, N, H)) return rc;
+  MH_REQUIRE(dout != nullptr && dz != nullptr, "tokattn_bwd_rows: null gradient buffer");
+  const int64_t NH = N * H;
+  int64_t g = (NH + 3) / 4;
+  if (g > 32768) g = 32768;
+  const TokRows tr{ids, ldid, tab0, (int)V};
+  if (g_tokattn_bwd_batched)
+    DISPATCH_T(dtype, (tokattn_bwd_kernel<T, TK, true, true><<<(int)g, 256, 0, (hipStream_t)stream>>>(
+                          (const T*)zc, (const T*)dout, (T*)dz, NH, TK, H, scale, cos_t, sin_t, rowscale, tr, (T*)dz_hid)));
+  else
+    DISPATCH_T(dtype, (tokattn_bwd_kernel<T, TK, false, true><<<(int)g, 256, 0, (hipStream_t)stream>>>(
+                          (const T*)zc, (const T*)dout, (T*)dz, NH, TK, H, scale, cos_t, sin_t, rowscale, tr, (T*)dz_hid)));
+  MH_LAUNCH_CHECK();
+  return MH_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------

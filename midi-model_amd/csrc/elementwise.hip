@@ -168,9 +168,15 @@ constexpr int SEG_OWN = 1024;
 template <typename T, int NCH, bool SL, int NW>
 __global__ __launch_bounds__(NW * 64) void embed_segment_bwd_kernel(const int64_t* __restrict__ src, const int64_t* __restrict__ seg,
                                                                 const T* __restrict__ dout, int64_t ld,
-                                                                float* __restrict__ dtab, int V, int D, int64_t n_occ,
-                                                                int pad_id) {
+                                                                float* __restrict__ dtab, int64_t ldt, int V, int Dtot, int Dslab,
+                                                                int64_t n_occ, int pad_id) {
   constexpr int N = Pack<T>::N;
+  // blockIdx.y = the slab of Dslab columns this workgroup sums (mh_embed_segment_sum: rows wider than the registers of one wave
+  // hold are cut into slabs that each run the narrow form; one slab = the whole row everywhere else)
+  const int col0 = blockIdx.y * Dslab;
+  const int D = (Dtot - col0 < Dslab) ? Dtot - col0 : Dslab;
+  dout += col0;
+  dtab += col0;
   constexpr int RW = 64, G = 4;  // occurrences per pass (one per lane), rows in flight; a nominal piece is 2 RW occurrences
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   extern __shared__ __attribute__((aligned(16))) int seg_l[];  // SL: seg_start[0 .. V] for the binary searches; behind it the waves' slots
@@ -207,7 +213,7 @@ __global__ __launch_bounds__(NW * 64) void embed_segment_bwd_kernel(const int64_
   int cur = -1;
   bool own = false;  // the run's id belongs to this wave alone
   auto flush = [&]() {
-    float* dst = dtab + (int64_t)cur * D;
+    float* dst = dtab + (int64_t)cur * ldt;
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
       const int c = (ch * 64 + lane) * N;
@@ -300,24 +306,21 @@ __global__ __launch_bounds__(NW * 64) void embed_segment_bwd_kernel(const int64_
   flush();
 }
 
-extern "C" int mh_embed_segment_bwd(const int64_t* src_rows, const int64_t* seg_start, const void* dout, int64_t ld,
-                                    float* dtable_f32, int64_t V, int D, int64_t n_occ, int64_t pad_id, int dtype,
-                                    void* stream) {
-  MH_REQUIRE(V > 0 && V < (1 << 30) && D % 8 == 0 && D <= 4096 && n_occ >= 0, "embed_segment_bwd: bad args");
-  MH_REQUIRE(dtype != MH_F32 || D <= 2048, "embed_segment_bwd: fp32 supports D <= 2048");
-  if (n_occ == 0) return MH_OK;
-  MH_REQUIRE(n_occ < (1ll << 31), "embed_segment_bwd: too many occurrences");
+// D columns in slabs of Dslab (<= 4096 bf16 / 2048 fp32 columns each), table rows ldt floats apart
+static int embed_segment_launch(const int64_t* src_rows, const int64_t* seg_start, const void* dout, int64_t ld, float* dtable_f32,
+                                int64_t ldt, int64_t V, int D, int Dslab, int64_t n_occ, int64_t pad_id, int dtype, void* stream) {
   const bool sl = (V + 1) * 4 <= 16 * 1024;  // seg_start fits the LDS beside the waves' slots (every vocabulary of the reference: 3406 / 3408 ids)
   const int seg_words = sl ? (int)((V + 1 + 3) & ~3) : 0;
   const int per = 64 * (dtype == MH_F32 ? 4 : 8);
-  const int nch = (D + per - 1) / per;
+  const int nch = (Dslab + per - 1) / per;
+  const unsigned nslab = (unsigned)((D + Dslab - 1) / Dslab);
   // 8 waves (1024 occurrences) per workgroup while the waves' slots (NCH x 64 lanes x 16 or 32 bytes each) fit beside seg_start
   // in 64 KiB of LDS, else 4, else 1 (D = 4096: no meeting, the r01 form)
 #define MH_SEG3(NCH_, SL_, NW_)                                                                                           \
   DISPATCH_T(dtype, (embed_segment_bwd_kernel<T, NCH_, SL_, NW_>                                                          \
-                     <<<(unsigned)((n_occ + NW_ * 128 - 1) / (NW_ * 128)), NW_ * 64,                                       \
+                     <<<dim3((unsigned)((n_occ + NW_ * 128 - 1) / (NW_ * 128)), nslab), NW_ * 64,                          \
                         (size_t)seg_words * 4 + (size_t)NW_ * NCH_ * 64 * Pack<T>::N * 4 + NW_ * 4, (hipStream_t)stream>>>( \
-                         src_rows, seg_start, (const T*)dout, ld, dtable_f32, (int)V, D, n_occ, (int)pad_id)))
+                         src_rows, seg_start, (const T*)dout, ld, dtable_f32, ldt, (int)V, D, Dslab, n_occ, (int)pad_id)))
 #define MH_SEG(NCH_)                                                                                                      \
   do {                                                                                                                    \
     if (NCH_ <= 2) { if (sl) MH_SEG3(NCH_, true, 8); else MH_SEG3(NCH_, false, 8); }                                       \
@@ -330,6 +333,99 @@ extern "C" int mh_embed_segment_bwd(const int64_t* src_rows, const int64_t* seg_
   else MH_SEG(8);
 #undef MH_SEG
 #undef MH_SEG3
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+extern "C" int mh_embed_segment_bwd(const int64_t* src_rows, const int64_t* seg_start, const void* dout, int64_t ld,
+                                    float* dtable_f32, int64_t V, int D, int64_t n_occ, int64_t pad_id, int dtype,
+                                    void* stream) {
+  MH_REQUIRE(V > 0 && V < (1 << 30) && D % 8 == 0 && D <= 4096 && n_occ >= 0, "embed_segment_bwd: bad args");
+  MH_REQUIRE(dtype != MH_F32 || D <= 2048, "embed_segment_bwd: fp32 supports D <= 2048");
+  if (n_occ == 0) return MH_OK;
+  MH_REQUIRE(n_occ < (1ll << 31), "embed_segment_bwd: too many occurrences");
+  return embed_segment_launch(src_rows, seg_start, dout, ld, dtable_f32, D, V, D, D, n_occ, pad_id, dtype, stream);
+}
+
+// The segment sum of WIDE rows (the first token-level block's d z, 3D columns, summed per input token id: engine.tok_first_backward):
+// sum_f32[v, :] += the rows src_rows[seg_start[v] .. seg_start[v + 1]) of `rows`, EVERY id included (a pad input in mid-sequence
+// carries gradient into the projection's weights).  The row is cut into slabs of 2 x 64 lanes x 16 bytes (1024 bf16 columns), one
+// grid row of workgroups per slab: each slab runs the 8-wave form of the D = 1024 embedding gradient -- its registers, its
+// meeting in LDS, its 2 KiB gathers -- instead of the one-wave form a 3072-wide row would fall to.
+extern "C" int mh_embed_segment_sum(const int64_t* src_rows, const int64_t* seg_start, const void* rows, int64_t ld, float* sum_f32,
+                                    int64_t ldsum, int64_t V, int D, int64_t n_occ, int dtype, void* stream) {
+  MH_REQUIRE(V > 0 && V < (1 << 30) && D > 0 && D % 8 == 0 && ld % 8 == 0 && ld >= D && ldsum % 4 == 0 && ldsum >= D && n_occ >= 0 &&
+                 rows != nullptr && sum_f32 != nullptr && (((uintptr_t)rows | (uintptr_t)sum_f32) & 15) == 0,
+             "embed_segment_sum: bad args V=%ld D=%d ld=%ld ldsum=%ld", (long)V, D, (long)ld, (long)ldsum);
+  if (n_occ == 0) return MH_OK;
+  MH_REQUIRE(n_occ < (1ll << 31), "embed_segment_sum: too many occurrences");
+  const int slab = 2 * 64 * (dtype == MH_F32 ? 4 : 8);
+  MH_REQUIRE((D + slab - 1) / slab < 65536, "embed_segment_sum: too many slabs");
+  return embed_segment_launch(src_rows, seg_start, rows, ld, sum_f32, ldsum, V, D, D < slab ? D : slab, n_occ, -1, dtype, stream);
+}
+
+// hi = round(s), lo = round(s - hi): an fp32 sum as two terms of the GEMMs' operand type, so that a product with it sees s to
+// ~2^-17 (bf16) instead of 2^-9.  n elements, a multiple of 4.
+template <typename T>
+__global__ __launch_bounds__(256) void split_hi_lo_kernel(const float* __restrict__ s, T* __restrict__ hi, T* __restrict__ lo, int64_t n4) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(s + 4 * i);
+    float h[4], l[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      h[e] = rnd<T>(v[e]);
+      l[e] = v[e] - h[e];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      hi[4 * i + e] = from_f<T>(h[e]);
+      lo[4 * i + e] = from_f<T>(l[e]);
+    }
+  }
+}
+extern "C" int mh_embed_split_hi_lo(const float* s, void* hi, void* lo, int64_t n, int dtype, void* stream) {
+  MH_REQUIRE(n > 0 && n % 4 == 0 && s != nullptr && hi != nullptr && lo != nullptr && ((uintptr_t)s & 15) == 0, "embed_split_hi_lo: bad args");
+  DISPATCH_T(dtype, (split_hi_lo_kernel<T><<<grid_for(n / 4, 256, 4096), 256, 0, (hipStream_t)stream>>>(s, (T*)hi, (T*)lo, n / 4)));
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// The folded RMSNorm's backward on the ROWS OF THE EMBEDDING TABLE (first token-level block; engine.tok_first_backward): with
+// T_v = t_hi[v] + t_lo[v] (fp32) = (sum over the occurrences of id v of d z) W',
+//   acc32[v, :] += T_v - e_v (rstd_v^2 / D) rowdot(T_v, e_v)
+// -- mh_rmsnorm_bwd_folded is linear in t for a fixed x, so the sum over an id's occurrences is taken before it.  Row `pad_id`
+// is left alone (nn.Embedding's padding_idx row has no gradient).  One wave per row.
+template <typename T>
+__global__ __launch_bounds__(256) void embed_table_norm_bwd_kernel(const T* __restrict__ t_hi, const T* __restrict__ t_lo,
+                                                                   const T* __restrict__ e, const float* __restrict__ rstd,
+                                                                   float* __restrict__ acc32, int64_t V, int D, int64_t pad_id) {
+  constexpr int N = Pack<T>::N;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int64_t v = (int64_t)blockIdx.x * 4 + wv; v < V; v += (int64_t)gridDim.x * 4) {
+    if (v == pad_id) continue;
+    const float r = rstd[v];
+    float dot = 0.f;
+    for (int c = lane * N; c < D; c += 64 * N) {
+      const Pack<T> hv = ld16(t_hi + v * D + c), lv = ld16(t_lo + v * D + c), ev = ld16(e + v * D + c);
+#pragma unroll
+      for (int k = 0; k < N; ++k) dot += (hv.get(k) + lv.get(k)) * ev.get(k);
+    }
+    const float cf = r * r * wave_sum(dot) / (float)D;
+    for (int c = lane * N; c < D; c += 64 * N) {
+      const Pack<T> hv = ld16(t_hi + v * D + c), lv = ld16(t_lo + v * D + c), ev = ld16(e + v * D + c);
+      float* dst = acc32 + v * D + c;
+#pragma unroll
+      for (int k = 0; k < N; ++k) dst[k] += (hv.get(k) + lv.get(k)) - ev.get(k) * cf;
+    }
+  }
+}
+extern "C" int mh_embed_table_norm_bwd(const void* t_hi, const void* t_lo, const void* e, const float* rstd, float* acc32, int64_t V,
+                                       int D, int64_t pad_id, int dtype, void* stream) {
+  MH_REQUIRE(V > 0 && D > 0 && D % 8 == 0 && t_hi != nullptr && t_lo != nullptr && e != nullptr && rstd != nullptr && acc32 != nullptr &&
+                 (((uintptr_t)t_hi | (uintptr_t)t_lo | (uintptr_t)e) & 15) == 0,
+             "embed_table_norm_bwd: bad arguments V=%ld D=%d", (long)V, D);
+  DISPATCH_T(dtype, (embed_table_norm_bwd_kernel<T><<<grid_for(V, 4, 65536), 256, 0, (hipStream_t)stream>>>(
+                        (const T*)t_hi, (const T*)t_lo, (const T*)e, rstd, acc32, V, D, pad_id)));
   MH_LAUNCH_CHECK();
   return MH_OK;
 }

@@ -15,7 +15,7 @@ import os
 
 import torch
 
-from . import ops
+from . import ops, tokfirst
 
 
 @dataclass
@@ -130,6 +130,7 @@ class StackSaved(NamedTuple):
     nseq: int
     slen: int
     folded: Optional[list]               # the folded weights the forward ran with; None: the plain blocks
+    first: Optional[tokfirst.TokFirst] = None   # layers[0] is tok_first_forward's (x = [hidden ; E ; E], qkv = its projection)
 
 
 def _norm_qkv(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, slen: int, rope: RopeTable, pos0: int, rope_in_attn: bool,
@@ -252,6 +253,19 @@ def layer_forward_folded(spec: StackSpec, lw: LayerTensors, fold, x: torch.Tenso
         ops.tokattn_fwd(qkv, o, nseq, slen, H, spec.scale, rope.cos, rope.sin)
     if kv_out is not None:
         kv_out.append(qkv)
+    x3, parts3, x2, rstd2, gu, a = _folded_o_mlp(spec, lw, wgu_n, x, o, rstd1, save)
+    if save:
+        saved_out.append(LayerSaved(x, rstd1, None, qkv, o, lse, x2, rstd2, None, gu, None if lean else a))
+    return x3, parts3
+
+
+def _folded_o_mlp(spec: StackSpec, lw: LayerTensors, wgu_n: torch.Tensor, x: torch.Tensor, o: torch.Tensor, rstd1: torch.Tensor,
+                  save: bool):
+    """Second half of the folded block, behind the attention: o projection + residual ``x`` with the row statistics of what it
+    stores -> rstd -> gate|up projection on the folded weights with the row scale and SwiGLU -> down projection + residual with
+    statistics.  Returns (x3, its parts, x2, rstd2, gu | None, a)."""
+    M, D = x.shape
+    I = spec.I
     parts = _empty((D // 64, M), x, torch.float32)
     x2 = _empty((M, D), x)
     ops.gemm_rowss(o, lw.wo, x2, parts, res=x)
@@ -264,8 +278,37 @@ def layer_forward_folded(spec: StackSpec, lw: LayerTensors, fold, x: torch.Tenso
     parts3 = _empty((D // 64, M), x, torch.float32) if save else parts
     x3 = _empty((M, D), x)
     ops.gemm_rowss(a, lw.wd, x3, parts3, res=x2)
-    if save:
-        saved_out.append(LayerSaved(x, rstd1, None, qkv, o, lse, x2, rstd2, None, gu, None if lean else a))
+    return x3, parts3, x2, rstd2, gu, a
+
+
+def tok_first_forward(spec: StackSpec, lw: LayerTensors, fold, first: tokfirst.TokFirst, x: torch.Tensor, nseq: int,
+                      rope: RopeTable, saved_out: list, lean: bool = False):
+    """layer_forward_folded (training form) for the FIRST block of the token-level stack, whose input rows ``x`` [nseq * 8, D] are
+    row 8n = first.hidden[n] and rows 8n + p = first.table[first.ids[n, p - 1]] (ops.concat_tok_fwd): the norm statistics and the
+    q|k|v projection run once over x_cat = [hidden ; table] -- nseq + V rows instead of 8 nseq -- and the attention kernel takes
+    its rows through the ids (tokfirst.tokattn_fwd_rows).  Same GEMM entry, same K loop, and a row's product does not depend on
+    the tile it falls in: every q|k|v value, hence ``o`` and everything behind it, equals the dense schedule's bit for bit.
+    The buffer is [hidden ; table ; table] (nseq + 2 V rows): the backward's weight gradient contracts [dz_h ; S_hi ; S_lo]
+    against it, and the row-scaled projection, which takes its rows in groups of 4, runs over round_up(nseq + V, 4) of them.
+    LayerSaved keeps x = that buffer and qkv = its projection in place of the [8 nseq, .] ones.  Returns (block output, its parts)."""
+    N, D = first.hidden.shape
+    V = first.table.shape[0]
+    H = spec.H
+    assert N == nseq and x.shape == (N * tokfirst.TN, D) and first.table.shape[1] == D
+    wq_n, wgu_n = fold
+    Mf = ops.round_up(N + V, 4)
+    xc = _empty((N + 2 * V, D), x)
+    xc[:N].copy_(first.hidden)
+    xc[N:N + V].copy_(first.table)
+    xc[N + V:].copy_(first.table)
+    rstd_c = _empty((Mf,), x, torch.float32)
+    ops.row_rstd(rstd_c, D, spec.eps, x=xc[:Mf])
+    zc = _empty((Mf, 3 * D), x)
+    ops.gemm_nt_scaled(xc[:Mf], wq_n, zc, rstd_c)
+    o = _empty((N * tokfirst.TN, D), x)
+    tokfirst.tokattn_fwd_rows(zc, first.ids, N, V, o, N, H, spec.scale, rope.cos, rope.sin)
+    x3, parts3, x2, rstd2, gu, a = _folded_o_mlp(spec, lw, wgu_n, x, o, rstd_c, True)
+    saved_out.append(LayerSaved(xc, rstd_c, None, zc, o, None, x2, rstd2, None, gu, None if lean else a))
     return x3, parts3
 
 
@@ -343,8 +386,28 @@ def layer_backward_folded(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, f
     dx = t - x (rstd^2 / D) rowdot(t, x) + dres the norm's backward without its weight, and the weight gradient G' = d z^T x
     turns into dW = G' (.) w and dw = colsum(G' (.) W) inside its split-K reduction (ops.wgrad_folded)."""
     M, D = dx.shape
-    H, I = spec.H, spec.I
+    H = spec.H
     wq_n, wgu_n = fold
+    dx2, do = _folded_mlp_o_backward(spec, lw, lg, wgu_n, keep, dx, accumulate)
+    dz1 = _empty((M, 3 * D), dx)
+    if spec.kind == "event":
+        ops.attn_bwd(keep.qkv, keep.o, do, keep.lse, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
+    else:
+        ops.tokattn_bwd(keep.qkv, do, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
+    t1 = do
+    ops.gemm_nt(dz1, wq_n, t1, tb=True)                      # t1 = d z1 @ W'qkv
+    ops.wgrad_folded(dz1, keep.x, lg.wqkv, lw.n1, lw.wqkv, lg.n1, accumulate)
+    del dz1
+    ops.rmsnorm_bwd_folded(keep.x, keep.rstd1, t1, dx2, dx)
+    return dx
+
+
+def _folded_mlp_o_backward(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, wgu_n: torch.Tensor, keep: LayerSaved,
+                           dx: torch.Tensor, accumulate: bool):
+    """The folded block's backward from its output down to the attention: the MLP half, then the o projection.
+    Returns (dx2 = the gradient of the residual stream between the halves, do = the gradient of the attention output)."""
+    M, D = dx.shape
+    I = spec.I
     # ---- MLP ----
     a = keep.a
     if a is None:
@@ -364,27 +427,71 @@ def layer_backward_folded(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, f
     do = t2                                                  # reuse
     ops.gemm_nt(dx2, lw.wo, do, tb=True)
     linear_wgrad(dx2, keep.o, lg.wo, accumulate)
-    dz1 = _empty((M, 3 * D), dx)
-    if spec.kind == "event":
-        ops.attn_bwd(keep.qkv, keep.o, do, keep.lse, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
-    else:
-        ops.tokattn_bwd(keep.qkv, do, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
-    t1 = do
-    ops.gemm_nt(dz1, wq_n, t1, tb=True)                      # t1 = d z1 @ W'qkv
-    ops.wgrad_folded(dz1, keep.x, lg.wqkv, lw.n1, lw.wqkv, lg.n1, accumulate)
-    del dz1
-    ops.rmsnorm_bwd_folded(keep.x, keep.rstd1, t1, dx2, dx)
-    return dx
+    return dx2, do
+
+
+class TokFirstGrads(NamedTuple):
+    """what tok_first_backward hands back in place of the gradient of the [8 N, D] input rows"""
+    dhidden: torch.Tensor   # [N, D] gradient of first.hidden
+    dtable32: torch.Tensor  # [V, D] fp32 gradient of first.table (row pad_id zero)
+
+
+def tok_first_backward(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, fold, keep: LayerSaved, first: tokfirst.TokFirst,
+                       dx: torch.Tensor, nseq: int, rope: RopeTable, accumulate: bool) -> TokFirstGrads:
+    """The backward of tok_first_forward.  Down to d z1 (the attention backward's stores, rows through the ids) it is
+    layer_backward_folded.  The rest is linear in d z1 for fixed inputs, and rows 8n + p (p >= 1) have one of V inputs, so with
+    S_v = the sum of d z1 over the rows whose input is table row v (pad id included: a pad in mid-sequence carries gradient
+    into W'), kept as two bf16 terms hi + lo (S to ~2^-17):
+      t_cat = [dz_h ; S_hi ; S_lo] W'                                (one dgrad over N + 2 V rows)
+      G'    = [dz_h ; S_hi ; S_lo]^T [hidden ; E ; E]                (one folded weight gradient, contraction N + 2 V)
+      d hidden = rmsnorm_bwd_folded(hidden, rstd_h, t_h, dres rows 8n)
+      d E_v = (T_hi + T_lo)_v - e_v (rstd_v^2 / D) rowdot(T_v, e_v) + the sum of dres over v's rows  (pad row: zero)
+    where dres = the gradient of the residual stream between the halves.  The occurrence lists are made once and serve both
+    segment sums; S is summed in a fixed order (tokfirst.occurrence_lists), without the atomics the embedding gradient allows
+    itself, because it reaches the weight gradients."""
+    M, D = dx.shape
+    H, T = spec.H, tokfirst.TN
+    N, V = first.hidden.shape[0], first.table.shape[0]
+    assert N == nseq and M == N * T
+    wq_n, wgu_n = fold
+    xc, rstd_c, zc = keep.x, keep.rstd1, keep.qkv
+    dres, do = _folded_mlp_o_backward(spec, lw, lg, wgu_n, keep, dx, accumulate)
+    dz = _empty((M, 3 * D), dx)                              # (rows 8n stay unwritten: they go to dzc[:N])
+    dzc = _empty((N + 2 * V, 3 * D), dx)                     # [dz_h ; S_hi ; S_lo]
+    tokfirst.tokattn_bwd_rows(zc, first.ids, N, V, do, dz, dzc[:N], rstd_c, N, H, spec.scale, rope.cos, rope.sin)
+    del do
+    # row 8n + p per occurrence, in a fixed order: S feeds weight gradients and must not vary from run to run
+    src, seg, vseg, vstart = tokfirst.occurrence_lists(first.ids[:, : T - 1], V, T, 1)
+    S = _empty((V, 3 * D), dx, torch.float32)
+    tokfirst.segment_sum_fixed_order(src, vseg, vstart, dz, S)
+    del dz
+    tokfirst.split_hi_lo(S, dzc[N:N + V], dzc[N + V:])
+    del S
+    tc = _empty((N + 2 * V, D), dx)
+    ops.gemm_nt(dzc, wq_n, tc, tb=True)                      # t_cat = [dz_h ; S_hi ; S_lo] @ W'qkv
+    ops.wgrad_folded(dzc, xc, lg.wqkv, lw.n1, lw.wqkv, lg.n1, accumulate)
+    del dzc
+    dres_h = _empty((N, D), dx)
+    ops.copy_rows(dres, T * D, dres_h, D, N, D)
+    dhid = _empty((N, D), dx)
+    ops.rmsnorm_bwd_folded(xc[:N], rstd_c[:N], tc[:N], dres_h, dhid)
+    acc32 = torch.zeros((V, D), dtype=torch.float32, device=dx.device)
+    ops.embed_segment_bwd(src, seg, dres, D, acc32, first.pad_id)
+    tokfirst.table_norm_bwd(tc[N:N + V], tc[N + V:], xc[N:N + V], rstd_c[N:N + V], acc32, first.pad_id)
+    return TokFirstGrads(dhid, acc32)
 
 
 def stack_forward(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable,
-                  save: bool, kv_out: Optional[list] = None, lean: bool = False, folded=None):
+                  save: bool, kv_out: Optional[list] = None, lean: bool = False, folded=None,
+                  first: Optional[tokfirst.TokFirst] = None):
     """x [nseq*slen, D] (inputs_embeds) -> (last_hidden_state [nseq*slen, D], StackSaved | None).
     save=True keeps what the backward needs (``lean``: minus the SwiGLU activations, recomputed in the backward);
     kv_out (prefill) receives each layer's post-RoPE qkv.  runs_folded picks the blocks: plain (layer_forward) or with the
     RMSNorms folded (layer_forward_folded).  ``folded`` = fold_norm_weights(W) kept current by the caller (a decode session's;
     MIDIModel.folded_weights, re-derived after every update -- the training forward takes no other, and the backward finds them
-    in the context); a forward-only pass without one makes the fold here, from the live weights, per call."""
+    in the context); a forward-only pass without one makes the fold here, from the live weights, per call.
+    ``first`` (token-level stack, training): what the rows ``x`` were laid out from; where the folded training blocks run and
+    tokfirst.table_first_ok holds, the first block takes tok_first_forward and stack_backward returns TokFirstGrads."""
     _check_heads(spec)
     M, D = x.shape
     assert M == nseq * slen
@@ -396,8 +503,12 @@ def stack_forward(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, 
         folded = None
     saved = [] if save else None
     parts = None
+    if not (save and folded is not None and tokfirst.table_first_ok(spec, first, slen)):
+        first = None
     for li, lw in enumerate(W.layers):
-        if folded is not None:
+        if first is not None and li == 0:
+            x, parts = tok_first_forward(spec, lw, folded[li], first, x, nseq, rope, saved, lean)
+        elif folded is not None:
             x, parts = layer_forward_folded(spec, lw, folded[li], x, nseq, slen, rope, parts, kv_out, saved, lean)
         else:
             x, keep = layer_forward(spec, lw, x, nseq, slen, rope, kv_out, save, lean and save)
@@ -407,20 +518,24 @@ def stack_forward(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, 
     # (the forward-only folded pass is the one form that asks the final norm for no rstd)
     rstdf = _empty((M,), x, torch.float32) if save or folded is None else None
     ops.rmsnorm_fwd(x, W.norm, y, rstdf, spec.eps)
-    return y, (StackSaved(saved, x, rstdf, nseq, slen, folded) if save else None)
+    return y, (StackSaved(saved, x, rstdf, nseq, slen, folded, first) if save else None)
 
 
 def stack_backward(spec: StackSpec, W: StackTensors, G: StackTensors, ctx: StackSaved, dy: torch.Tensor,
                    rope: RopeTable, accumulate: bool, on_layer_done: Optional[Callable[[int], None]] = None):
     """dy = d loss / d last_hidden_state  ->  d loss / d inputs_embeds; parameter gradients go to G
     (overwritten, or added to when `accumulate`).  `on_layer_done(i)` fires when layer i's gradients are
-    final (layers finish in reverse order) — the data-parallel reducer hangs its bucket launches on it."""
+    final (layers finish in reverse order) — the data-parallel reducer hangs its bucket launches on it.
+    Where the forward ran tok_first_forward (ctx.first) the result is TokFirstGrads: the gradients of the hidden states and of
+    the embedding table the input rows were laid out from."""
     M, D = dy.shape
     dx = _empty((M, D), dy)
     ops.rmsnorm_bwd(ctx.x_last, W.norm, ctx.rstdf, dy, None, dx, G.norm, accumulate)
     for li in range(len(W.layers) - 1, -1, -1):
         lw, lg = W.layers[li], G.layers[li]
-        if ctx.folded is not None:
+        if ctx.first is not None and li == 0:
+            dx = tok_first_backward(spec, lw, lg, ctx.folded[li], ctx.layers[li], ctx.first, dx, ctx.nseq, rope, accumulate)
+        elif ctx.folded is not None:
             dx = layer_backward_folded(spec, lw, lg, ctx.folded[li], ctx.layers[li], dx, ctx.nseq, ctx.slen, rope, accumulate)
         else:
             dx = layer_backward(spec, lw, lg, ctx.layers[li], dx, ctx.nseq, ctx.slen, rope, accumulate)

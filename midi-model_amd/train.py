@@ -22,7 +22,7 @@ from typing import Callable, List, Optional, Tuple
 
 import torch
 
-from . import engine, mixed, ops
+from . import engine, mixed, ops, tokfirst
 from .config import MIDIModelConfig
 from .model import MIDIModel
 
@@ -209,6 +209,10 @@ class TrainMIDIModel(MIDIModel):
         # no passes over the residual stream for the norms' forward, no normalised activations kept, the norm weights' gradients
         # out of the weight-gradient reductions.  bf16 only (engine.train_fold_ok); False = the r01-r05 schedule.
         self.fold_train_norms = True
+        # the first token-level block of that folded step per vocabulary entry (engine.tok_first_forward / tok_first_backward): the
+        # embedding table is projected once instead of once per row, the output gradient is summed per token id before the dgrad,
+        # the weight gradient and the norm's backward.  Same forward bits; False (or MH_TOK_TABLE=0) = every block dense.
+        self.tok_table_first = True
         self.force_reduce = False  # run the bucketed exchange even with one rank (tests, bench.py's contention probe)
         self._lora = None          # LoraAdapter while fine-tuning adapters on a frozen base (add_adapter)
 
@@ -610,8 +614,10 @@ class TrainMIDIModel(MIDIModel):
         # ---- forward: token-level net over [hidden ; embed(y[:, :7])]
         seq = torch.empty((N, T, D), dtype=dty, device=dev)
         ops.concat_tok_fwd(hidden_t, y_t, Wt.embed, seq, T)
+        first = tokfirst.TokFirst(hidden_t, y_t, Wt.embed, tok.pad_id) if (backward and self.tok_table_first) else None
         h, ctx_tok = engine.stack_forward(tspec, Wt, seq.view(R, D), N, T, self.rope("net_token"), save=backward,
-                                          lean=self.lean_activations, folded=self._train_fold(tspec, seq.view(R, D), backward))
+                                          lean=self.lean_activations, folded=self._train_fold(tspec, seq.view(R, D), backward),
+                                          first=first)
         del seq
 
         # ---- lm_head + cross-entropy (+ their backward), chunked over rows
@@ -672,14 +678,19 @@ class TrainMIDIModel(MIDIModel):
         dseq = engine.stack_backward(tspec, Wt, self._G["net_token"], ctx_tok, dh,
                                      self.rope("net_token"), accumulate, tok_done)
         del dh, ctx_tok
-        acc32 = torch.zeros((V, D), dtype=torch.float32, device=dev)
-        src, seg = ops.token_segments(y_t[:, : T - 1], V, row_mul=T, col_mul=1, add=1)  # row of dseq per occurrence
-        ops.embed_segment_bwd(src, seg, dseq, D, acc32, tok.pad_id)
+        per_id = isinstance(dseq, engine.TokFirstGrads)  # the first block ran per vocabulary entry: both gradients come out of it
+        if per_id:
+            dhid_t, acc32 = dseq
+        else:
+            acc32 = torch.zeros((V, D), dtype=torch.float32, device=dev)
+            src, seg = ops.token_segments(y_t[:, : T - 1], V, row_mul=T, col_mul=1, add=1)  # row of dseq per occurrence
+            ops.embed_segment_bwd(src, seg, dseq, D, acc32, tok.pad_id)
         ops.cast_from_f32(acc32, self._G["net_token"].embed, accumulate)
         o, n, _ = self._offsets["net_token.embed_tokens.weight"]
         self._announce(red, o, o + n)
-        dhid_t = torch.empty((N, D), dtype=dty, device=dev)
-        ops.copy_rows(dseq, T * D, dhid_t, D, N, D)
+        if not per_id:
+            dhid_t = torch.empty((N, D), dtype=dty, device=dev)
+            ops.copy_rows(dseq, T * D, dhid_t, D, N, D)
         del dseq
         if sel is not None:
             dhidden = torch.zeros((B, S, D), dtype=dty, device=dev)
