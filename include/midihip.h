@@ -274,6 +274,30 @@ int mh_attn_bwd_o(const void* qkv, const void* o, const void* dout, const float*
 int mh_attn_bwd_o_scaled(const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
                          const float* rowscale, int64_t B, int64_t S, int H, float scale, const float* cos_t, const float* sin_t,
                          int dtype, void* stream);
+
+/* Packed batches (table form).  qkv [M, 3*H*64] holds n sequences of any length >= 1 laid end to end: seq_start (device int32
+ * [n + 1], ascending, seq_start[0] = 0, seq_start[n] = M); sequence i is rows [seq_start[i], seq_start[i+1]), causal within itself, and
+ * sees nothing outside itself.  ONE launch per kernel whatever n is: `work` (device int32 [nwork][4], nwork a multiple of 8) is the
+ * launch order, built on the host from the lengths -- item = {sequence or -1 for an empty slot, head, 128-row tile rank counted from
+ * the sequence's first row (0 = the heaviest tile), the sequence's first row in the 64-padded scratch}; items b, b + 8, .. run on
+ * one XCD and hold all tiles of a (sequence, head) pair, heavy tiles first (midi_model_amd.ops.attn_seq_plan builds seq_start, pos,
+ * work, Mpad = sum of the lengths rounded up to 64 each, and max_len = the longest sequence: a sequence is addressed with
+ * 32-bit offsets from its first row, so max_len * 3 * H * 64 < 2^31; M and Mpad only have to fit an int32).  The tables are not
+ * validated on the device.
+ *   mh_rope_pos       mh_rope with row m rotated at pos[m] (device int32 [M]); dir = +1 / -1, both dtypes, mh_rope's roundings.
+ *   mh_attn_fwd_seqs  o [M, H*64], lse [H, M] (fp32, natural log).  bf16: the third-form MFMA kernel at the default "attn_v3" (255);
+ *                     any other value, and fp32, is MH_ERR_ARG with a message (as mh_attn_bwd_o) -- never another computation.
+ *   mh_attn_bwd_seqs  mh_attn_bwd_o on the table: scratch = fp32 [2 * H * Mpad]; rowscale (optional: row m of dqkv times
+ *                     rowscale[m], as mh_attn_bwd_o_scaled); cos_t / sin_t (optional): the rotation back at position = row minus its
+ *                     sequence's start, in the stores.  bf16 only.
+ * (fp32, the verification dtype: midi_model_amd.ops runs the uniform entry points sequence by sequence -- DESIGN.md 7.3.)           */
+int mh_rope_pos(void* qkv, const float* cos_t, const float* sin_t, const int32_t* pos, int64_t M, int H, int hd, int dir,
+                int dtype, void* stream);
+int mh_attn_fwd_seqs(const void* qkv, const int32_t* seq_start, const int32_t* work, int64_t nwork, void* o, float* lse,
+                     int64_t M, int64_t max_len, int H, float scale, int dtype, void* stream);
+int mh_attn_bwd_seqs(const void* qkv, const void* o, const void* dout, const float* lse, float* scratch, void* dqkv,
+                     const float* rowscale, const int32_t* seq_start, const int32_t* work, int64_t nwork, int64_t M,
+                     int64_t Mpad, int64_t max_len, int H, float scale, const float* cos_t, const float* sin_t, int dtype, void* stream);
 /* measurement aid, A/B library only (the production library returns MH_ERR_UNSUPPORTED): the production bf16 forward with shader-clock
  * stamps at the seams of each key tile's segments; stamps: uint32 [16][4][32][9] (tools/attn_timeline.py decodes them).        */
 int mh_attn_fwd_timeline(const void* qkv, void* o, float* lse, int64_t B, int64_t S, int H, float scale, int lazy,

@@ -281,21 +281,39 @@ __device__ inline void fwd3_tile(const char* tK, const char* tV, const int (&tro
 
 constexpr int TL_TILES = 32, TL_FIRST = 8, TL_STAMPS = 9;  // timeline build: tiles TL_FIRST .. +31 of a workgroup's loop, 9 stamps each
 constexpr int TL_BYTES = 4 * TL_TILES * TL_STAMPS * 4;       // 4 waves x 32-bit stamps = 4608 bytes behind the stages (still 3 workgroups per CU)
+// SQ: the table form (attn_mfma_common.h: AttnSeqs, handed over as ONE trailing argument that the uniform instantiations do not have).
+// It changes the three kernels' preambles only -- which rows are the sequence, where its statistics lie -- and the uniform
+// instantiations compile to what they were (disassembly compared function by function: DESIGN.md 7.3).  Table form: S, Sp, BH, nqt and
+// nqt_all are ignored, lse is [H, M].
 template <int WPS, bool TR, int NS = 2 /* K/V stages in LDS: tile kt + NS - 1 is requested while tile kt is computed */, bool LZ = false,
-          bool TL = false /* timeline build: `vt` is the uint32 output [16 workgroups][4 waves][TL_TILES][TL_STAMPS] */>
+          bool TL = false /* timeline build: `vt` is the uint32 output [16 workgroups][4 waves][TL_TILES][TL_STAMPS] */,
+          bool SQ = false, typename... SQT>
 __global__ __launch_bounds__(256, WPS) void attn_fwd3_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ vt,
                                                           bf16* __restrict__ o, float* __restrict__ lse, int S, int Sp, int H,
                                                           float sc /* scale*log2(e) */, int BH, int nqt,
                                                           int nqt_all /* 128-row query tiles of the sequence; the launch covers the
-                                                                         LAST nqt of them (mh_attn_fwd_tail: a chunk behind cached rows) */) {
+                                                                         LAST nqt of them (mh_attn_fwd_tail: a chunk behind cached rows) */,
+                                                          SQT... sqt) {
+  static_assert(sizeof...(SQT) == (SQ ? 1 : 0) && (!SQ || (TR && !TL)), "table form: one AttnSeqs, transpose reads, no timeline");
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 4 tiles = [stage][K | V^T] (dynamic: see attn_fwd_kernel)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int bh_, tile_;
-  if (!attn_work(BH, nqt, bh_, tile_)) return;
+  int sq_start = 0, sq_h = 0, sq_soff = 0, sq_M = 0;
+  if constexpr (SQ) {
+    const AttnSeqs& sq = attn_seqs_arg(sqt...);
+    if (!attn_work_seqs(sq, sq_start, S, sq_h, tile_, sq_soff)) return;
+    bh_ = 0;
+    sq_M = sq.M;
+    nqt_all = (S + 127) >> 7;
+  } else {
+    if (!attn_work(BH, nqt, bh_, tile_)) return;
+  }
   const int64_t bh = bh_;
   const int64_t b = bh / H;
-  const int h = (int)(bh - b * H);
+  const int h = SQ ? sq_h : (int)(bh - b * H);
+  auto row0 = [&]() -> int64_t { if constexpr (SQ) return (int64_t)sq_start; else return b * S; };  // first row of the sequence in qkv / o
+  auto lse0 = [&]() -> int64_t { if constexpr (SQ) return (int64_t)sq_h * sq_M + sq_start; else return bh * Sp; };
   const int64_t D = (int64_t)H * HD, D3 = 3 * D;
   const int q0 = (nqt_all - 1 - tile_) * 128;  // heavy (late) query tiles first
   const int qw0 = q0 + wave * 32;
@@ -303,7 +321,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd3_kernel(const bf16* __restr
   const int qrow = qw0 + li;
   const int qld = (qrow < S) ? qrow : S - 1;
 
-  const bf16* kbase = qkv + b * S * D3 + D + (int64_t)h * HD;
+  const bf16* kbase = qkv + row0() * D3 + D + (int64_t)h * HD;
   const bf16* vtbase = (TR || TL) ? kbase + D : vt + bh * HD * Sp;  // (TR: V row-major, straight out of the fused qkv rows)
   uint64_t tl_t0 = 0;
   int tl_first = TL_FIRST;  // first recorded tile: the word behind the census, written by the host (default 8)
@@ -325,7 +343,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd3_kernel(const bf16* __restr
 
   bf16x8 qf[4];
   {
-    const bf16* qp = qkv + (b * S + qld) * D3 + (int64_t)h * HD + 8 * hi;
+    const bf16* qp = qkv + (row0() + qld) * D3 + (int64_t)h * HD + 8 * hi;
 #pragma unroll
     for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
   }
@@ -437,7 +455,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd3_kernel(const bf16* __restr
   const float lt = l + __shfl_xor(l, 32, 64);
   if (qrow < S) {
     const float inv = 1.f / lt;
-    bf16* orow = o + (b * S + qrow) * D + (int64_t)h * HD;
+    bf16* orow = o + (row0() + qrow) * D + (int64_t)h * HD;
 #pragma unroll
     for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -447,7 +465,7 @@ __global__ __launch_bounds__(256, WPS) void attn_fwd3_kernel(const bf16* __restr
         for (int e = 0; e < 8; ++e) v[e] = (bf16)(oacc[db][8 * r8 + e] * inv);
         *reinterpret_cast<bf16x8*>(orow + db * 32 + 16 * r8 + 8 * hi) = v;
       }
-    if (hi == 0) lse[bh * Sp + qrow] = (m + log2f(lt)) * 0.6931471805599453f;
+    if (hi == 0) lse[lse0() + qrow] = (m + log2f(lt)) * 0.6931471805599453f;
   }
 }
 
@@ -535,7 +553,7 @@ __device__ inline void dq3_tile(const char* tK, const char* tV, const char* tKT,
   dq3_half<MASK, TR, 1>(tK, tV, tKT, tkt, foff, qf, dof, dqacc, hi, qrel, sc, lse2, dlt);
 }
 
-template <int WPS, bool TR>
+template <int WPS, bool TR, bool SQ = false, typename... SQT>
 __global__ __launch_bounds__(256, WPS) void attn_bwd_dq3_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ dout,
                                                               const float* __restrict__ lse, const float* __restrict__ delta,
                                                               const bf16* __restrict__ kt_, bf16* __restrict__ dqkv, int S,
@@ -544,16 +562,32 @@ __global__ __launch_bounds__(256, WPS) void attn_bwd_dq3_kernel(const bf16* __re
                                                               const float* __restrict__ sin_t,
                                                               const bf16* __restrict__ o_ /* != NULL: delta is computed here */,
                                                               float* __restrict__ delta_w,
-                                                              const float* __restrict__ rowscale /* != NULL: row m of dqkv times rowscale[m] */) {
+                                                              const float* __restrict__ rowscale /* != NULL: row m of dqkv times rowscale[m] */,
+                                                              SQT... sqt /* table form (see attn_fwd3_kernel): lse [H, M], delta_w [2][H][Mpad] */) {
+  static_assert(sizeof...(SQT) == (SQ ? 1 : 0) && (!SQ || TR), "table form: one AttnSeqs, transpose reads");
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [stage][K | V | K^T], or [stage][K | V] with transpose reads
   constexpr int NT = TR ? 2 : 3;  // tiles per stage
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int bh_, tile_;
-  if (!attn_work(BH, nqt, bh_, tile_)) return;
+  int sq_start = 0, sq_h = 0, sq_soff = 0, sq_M = 0, sq_Mpad = 0;
+  if constexpr (SQ) {
+    const AttnSeqs& sq = attn_seqs_arg(sqt...);
+    if (!attn_work_seqs(sq, sq_start, S, sq_h, tile_, sq_soff)) return;
+    bh_ = 0;
+    sq_M = sq.M;
+    sq_Mpad = sq.Mpad;
+    nqt = (S + 127) >> 7;
+  } else {
+    if (!attn_work(BH, nqt, bh_, tile_)) return;
+  }
   const int64_t bh = bh_;
   const int64_t b = bh / H;
-  const int h = (int)(bh - b * H);
+  const int h = SQ ? sq_h : (int)(bh - b * H);
+  const int64_t row0 = SQ ? (int64_t)sq_start : b * S;  // first row of the sequence in qkv / dout / dqkv
+  const int64_t lse0 = SQ ? (int64_t)sq_h * sq_M + sq_start : bh * Sp;
+  const int64_t dw0 = SQ ? (int64_t)sq_h * sq_Mpad + sq_soff : bh * Sp;  // the sequence's row of the scratch, and the scratch's second half
+  const int64_t dwh = SQ ? (int64_t)H * sq_Mpad : (int64_t)BH * Sp;
   const int64_t D = (int64_t)H * HD, D3 = 3 * D;
   const int q0 = (nqt - 1 - tile_) * 128;
   const int qw0 = q0 + wave * 32;
@@ -562,18 +596,18 @@ __global__ __launch_bounds__(256, WPS) void attn_bwd_dq3_kernel(const bf16* __re
   const int qld = (qrow < S) ? qrow : S - 1;
   const float sc = scale * LOG2E;
 
-  const bf16* kbase = qkv + b * S * D3 + D + (int64_t)h * HD;
+  const bf16* kbase = qkv + row0 * D3 + D + (int64_t)h * HD;
   const bf16* vbase = kbase + D;
   const bf16* ktbase = TR ? nullptr : kt_ + bh * HD * Sp;
 
   bf16x8 qf[4], dof[4];
   float dl = 0.f;
   {
-    const bf16* qp = qkv + (b * S + qld) * D3 + (int64_t)h * HD + 8 * hi;
-    const bf16* dp = dout + (b * S + qld) * D + (int64_t)h * HD + 8 * hi;
+    const bf16* qp = qkv + (row0 + qld) * D3 + (int64_t)h * HD + 8 * hi;
+    const bf16* dp = dout + (row0 + qld) * D + (int64_t)h * HD + 8 * hi;
     bf16x8 of[4];
     if (o_ != nullptr) {
-      const bf16* op = o_ + (b * S + qld) * D + (int64_t)h * HD + 8 * hi;
+      const bf16* op = o_ + (row0 + qld) * D + (int64_t)h * HD + 8 * hi;
 #pragma unroll
       for (int s = 0; s < 4; ++s) of[s] = *reinterpret_cast<const bf16x8*>(op + 16 * s);
     }
@@ -589,17 +623,17 @@ __global__ __launch_bounds__(256, WPS) void attn_bwd_dq3_kernel(const bf16* __re
       }
     }
   }
-  float lse2 = lse[bh * Sp + qld] * LOG2E;
+  float lse2 = lse[lse0 + qld] * LOG2E;
   if (o_ != nullptr) {
     // delta = rowsum(dO * O) of this lane's query row: the two half-waves hold 32 of the 64 columns each; the dK/dV kernel
     // (launched behind this one) reads it from delta_w -- no pass of its own over O and dO
     dl += __shfl_xor(dl, 32, 64);
     if (hi == 0 && qrow < S) {
-      delta_w[bh * Sp + qrow] = dl;
-      delta_w[(int64_t)BH * Sp + bh * Sp + qrow] = -lse2;  // second half of the scratch: -lse * log2(e) for the dK/dV kernel
+      delta_w[dw0 + qrow] = dl;
+      delta_w[dwh + dw0 + qrow] = -lse2;  // second half of the scratch: -lse * log2(e) for the dK/dV kernel
     }
   } else {
-    dl = delta[bh * Sp + qld];
+    dl = delta[dw0 + qld];
   }
   f32x16 dlt;
 #pragma unroll
@@ -663,10 +697,10 @@ __global__ __launch_bounds__(256, WPS) void attn_bwd_dq3_kernel(const bf16* __re
     __syncthreads();
   }
   if (qrow < S) {
-    bf16* orow = dqkv + (b * S + qrow) * D3 + (int64_t)h * HD;
+    bf16* orow = dqkv + (row0 + qrow) * D3 + (int64_t)h * HD;
     // (rowscale, r06: the q|k|v projection sits behind a FOLDED RMSNorm -- the stored gradient is the one of the unscaled
     //  product x W'^T, rstd (.) d qkv, which both the folded dgrad and the folded weight gradient take)
-    const float rsc = rowscale != nullptr ? rowscale[b * S + qrow] : 1.f;
+    const float rsc = rowscale != nullptr ? rowscale[row0 + qrow] : 1.f;
     store_grad_row(orow, dqacc, -scale * rsc, hi, cos_t, sin_t, qrow);  // (the accumulator holds -dQ)
   }
 }
@@ -785,24 +819,38 @@ __device__ inline void dkv3_tile(const char* tQ, const char* tDO, const char* tQ
   dkv3_half<MASK, TR, 1, PS>(tQ, tDO, tQT, tDOT, tLD, tq, tdo, foff, kf, vf, dkacc, dvacc, hi, krel, qlim, sc);
 }
 
-template <bool TR, bool PS = false /* lse holds -lse * log2(e) (mh_attn_bwd_o: written by the dQ kernel) */>
+template <bool TR, bool PS = false /* lse holds -lse * log2(e) (mh_attn_bwd_o: written by the dQ kernel) */, bool SQ = false,
+          typename... SQT>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ dout,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                const bf16* __restrict__ qt_, const bf16* __restrict__ dot_,
                                                                bf16* __restrict__ dqkv, int S, int Sp, int H, float scale,
                                                                int BH, int nkt, const float* __restrict__ cos_t,
                                                                const float* __restrict__ sin_t,
-                                                               const float* __restrict__ rowscale /* see attn_bwd_dq3_kernel */) {
+                                                               const float* __restrict__ rowscale /* see attn_bwd_dq3_kernel */,
+                                                               SQT... sqt /* table form (see attn_fwd3_kernel): lse / delta = the halves of the
+                                                                             scratch the dQ kernel wrote, [H][Mpad] each */) {
+  static_assert(sizeof...(SQT) == (SQ ? 1 : 0) && (!SQ || (TR && PS)), "table form: one AttnSeqs, transpose reads, statistics from dQ");
   // one stage: [Q | dO | Q^T | dO^T | lse (256 B of a KiB) | delta (256 B of a KiB)], with transpose reads [Q | dO | lse | delta]
   constexpr int NT = TR ? 2 : 4, STG = NT * TILE64 + 2048;
   extern __shared__ __attribute__((aligned(16))) char smem[];  // 2 stages
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int bh_, tile_;
-  if (!attn_work(BH, nkt, bh_, tile_)) return;
+  int sq_start = 0, sq_h = 0, sq_soff = 0, sq_Mpad = 0;
+  if constexpr (SQ) {
+    const AttnSeqs& sq = attn_seqs_arg(sqt...);
+    if (!attn_work_seqs(sq, sq_start, S, sq_h, tile_, sq_soff)) return;
+    bh_ = 0;
+    sq_Mpad = sq.Mpad;
+  } else {
+    if (!attn_work(BH, nkt, bh_, tile_)) return;
+  }
   const int64_t bh = bh_;
   const int64_t b = bh / H;
-  const int h = (int)(bh - b * H);
+  const int h = SQ ? sq_h : (int)(bh - b * H);
+  const int64_t row0 = SQ ? (int64_t)sq_start : b * S;  // first row of the sequence in qkv / dout / dqkv
+  auto st0 = [&]() -> int64_t { if constexpr (SQ) return (int64_t)sq_h * sq_Mpad + sq_soff; else return bh * Sp; };  // its statistics (a multiple of 64: 16-byte LDS-DMA requests)
   const int64_t D = (int64_t)H * HD, D3 = 3 * D;
   const int k0 = tile_ * 128;
   const int kw0 = k0 + wave * 32;
@@ -811,16 +859,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const bf16* __res
   const int kld = (krow < S) ? krow : S - 1;
   const float sc = scale * LOG2E;
 
-  const bf16* qbase = qkv + b * S * D3 + (int64_t)h * HD;
-  const bf16* dobase = dout + b * S * D + (int64_t)h * HD;
+  const bf16* qbase = qkv + row0 * D3 + (int64_t)h * HD;
+  const bf16* dobase = dout + row0 * D + (int64_t)h * HD;
   const bf16* qtbase = TR ? nullptr : qt_ + bh * HD * Sp;
   const bf16* dotbase = TR ? nullptr : dot_ + bh * HD * Sp;
-  const float* lse_b = lse + bh * Sp;
-  const float* delta_b = delta + bh * Sp;
+  const float* lse_b = lse + st0();
+  const float* delta_b = delta + st0();
 
   bf16x8 kf[4], vf[4];
   {
-    const bf16* kp = qkv + (b * S + kld) * D3 + D + (int64_t)h * HD + 8 * hi;
+    const bf16* kp = qkv + (row0 + kld) * D3 + D + (int64_t)h * HD + 8 * hi;
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       kf[s] = *reinterpret_cast<const bf16x8*>(kp + 16 * s);
@@ -905,8 +953,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkv3_kernel(const bf16* __res
     __syncthreads();
   }
   if (krow < S) {
-    bf16* krow_out = dqkv + (b * S + krow) * D3 + D + (int64_t)h * HD;
-    const float rsc = rowscale != nullptr ? rowscale[b * S + krow] : 1.f;
+    bf16* krow_out = dqkv + (row0 + krow) * D3 + D + (int64_t)h * HD;
+    const float rsc = rowscale != nullptr ? rowscale[row0 + krow] : 1.f;
     store_grad_row(krow_out, dkacc, -scale * rsc, hi, cos_t, sin_t, krow);  // (the accumulator holds -dK)
     store_grad_row(krow_out + D, dvacc, rsc, hi, nullptr, nullptr, 0);
   }
@@ -1024,5 +1072,46 @@ int mh_attn_bwd_mfma3(const void* qkv, const void* dout, const float* lse, const
                                                                   cos_t, sin_t, g_attn_bwd_rowscale);
     MH_LAUNCH_CHECK();
   }
+  return MH_OK;
+}
+
+// Table form of the three kernels (AttnSeqs, attn_mfma_common.h): ONE launch each whatever the number of sequences; the grid is the
+// work list.  The default forms only (attn_v3 = 255: three K/V stages, lazy reference maximum, transpose reads, delta inside dQ;
+// attn_v3_wps and attn_passes are not consulted: the register budgets are the defaults' and the order is the list's).
+static int attn_seqs_check(const char* who, const int32_t* seq_start, const int32_t* work, int64_t nwork, int64_t M, int64_t Mpad,
+                           int64_t max_len, int H) {
+  MH_REQUIRE(g_attn_v3 == 255, "%s: served by the default forms of the attention kernels only (attn_v3 = 255, not %d)", who, g_attn_v3);
+  MH_REQUIRE(seq_start != nullptr && work != nullptr && nwork > 0 && nwork % 8 == 0 && nwork < (int64_t(1) << 31),
+             "%s: needs seq_start and a work list of a multiple of 8 items (ops.attn_seq_plan)", who);
+  // (a sequence's rows are addressed from ITS first row with 32-bit offsets, as the uniform kernels address a (batch, head) panel: the
+  //  bound is on the longest sequence, not on M; the sequences' bases, lse and the statistics' rows are formed in 64 bits)
+  MH_REQUIRE(M > 0 && H > 0 && Mpad >= M && Mpad % 64 == 0 && M < (int64_t(1) << 31) && Mpad < (int64_t(1) << 31) && max_len >= 1 &&
+             max_len <= M && max_len * 3 * H * HD < (int64_t(1) << 31), "%s: bad shape (rows, or a sequence too long for 32-bit panel offsets)", who);
+  return MH_OK;
+}
+int mh_attn_fwd_seqs_mfma3(const void* qkv, const int32_t* seq_start, const int32_t* work, int64_t nwork, void* o, float* lse,
+                           int64_t M, int64_t max_len, int H, float scale, hipStream_t st) {
+  int rc = attn_seqs_check("attn_fwd_seqs", seq_start, work, nwork, M, (M + 63) / 64 * 64, max_len, H);
+  if (rc != MH_OK) return rc;
+  const AttnSeqs sq{seq_start, reinterpret_cast<const int4*>(work), (int)M, 0};
+  attn_fwd3_kernel<2, true, 3, true, false, true, AttnSeqs><<<(unsigned)nwork, 256, 6 * TILE64, st>>>((const bf16*)qkv, nullptr, (bf16*)o, lse, 0, 0, H,
+                                                                                                    scale * LOG2E, 0, 0, 0, sq);
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+int mh_attn_bwd_seqs_mfma3(const void* qkv, const void* o, const void* dout, const float* lse, float* scratch, void* dqkv,
+                           const float* rowscale, const int32_t* seq_start, const int32_t* work, int64_t nwork, int64_t M,
+                           int64_t Mpad, int64_t max_len, int H, float scale, const float* cos_t, const float* sin_t, hipStream_t st) {
+  int rc = attn_seqs_check("attn_bwd_seqs", seq_start, work, nwork, M, Mpad, max_len, H);
+  if (rc != MH_OK) return rc;
+  const AttnSeqs sq{seq_start, reinterpret_cast<const int4*>(work), (int)M, (int)Mpad};
+  attn_bwd_dq3_kernel<3, true, true, AttnSeqs><<<(unsigned)nwork, 256, 4 * TILE64, st>>>((const bf16*)qkv, (const bf16*)dout, lse, nullptr, nullptr,
+                                                                                       (bf16*)dqkv, 0, 0, H, scale, 0, 0, cos_t, sin_t, (const bf16*)o,
+                                                                                       scratch, rowscale, sq);
+  MH_LAUNCH_CHECK();
+  attn_bwd_dkv3_kernel<true, true, true, AttnSeqs><<<(unsigned)nwork, 256, 2 * (2 * TILE64 + 2048), st>>>(
+      (const bf16*)qkv, (const bf16*)dout, scratch + (int64_t)H * Mpad, scratch, nullptr, nullptr, (bf16*)dqkv, 0, 0, H, scale, 0, 0, cos_t, sin_t,
+      rowscale, sq);
+  MH_LAUNCH_CHECK();
   return MH_OK;
 }

@@ -1300,3 +1300,37 @@ extern "C" int mh_attn_bwd_o(const void* qkv, const void* o, const void* dout, c
   MH_REQUIRE(dtype == MH_BF16, "attn_bwd_o: bf16 only (fp32: mh_attn_prep_bwd + mh_attn_bwd)");
   return mh_attn_bwd_o_mfma(qkv, o, dout, lse, delta, dqkv, B, S, H, scale, cos_t, sin_t, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Table form: qkv [M, 3*H*64] holds n sequences laid end to end (seq_start int32 [n + 1] on the device), each causal within itself
+// and blind to the others; `work` is the launch order the host built from the lengths (ops.attn_seq_plan; attn_mfma_common.h: AttnSeqs).  ONE
+// launch per kernel whatever n is.  lse is [H, M].  bf16 only: the default forms of the MFMA kernels.
+// ---------------------------------------------------------------------------------------------------
+int mh_attn_fwd_seqs_mfma3(const void* qkv, const int32_t* seq_start, const int32_t* work, int64_t nwork, void* o, float* lse,
+                           int64_t M, int64_t max_len, int H, float scale, hipStream_t st);  // attention_mfma3.hip
+int mh_attn_bwd_seqs_mfma3(const void* qkv, const void* o, const void* dout, const float* lse, float* scratch, void* dqkv,
+                           const float* rowscale, const int32_t* seq_start, const int32_t* work, int64_t nwork, int64_t M,
+                           int64_t Mpad, int64_t max_len, int H, float scale, const float* cos_t, const float* sin_t, hipStream_t st);
+
+extern "C" int mh_attn_fwd_seqs(const void* qkv, const int32_t* seq_start, const int32_t* work, int64_t nwork, void* o, float* lse,
+                                int64_t M, int64_t max_len, int H, float scale, int dtype, void* stream) {
+  MH_REQUIRE(M > 0 && H > 0 && seq_start != nullptr && work != nullptr && nwork > 0 && nwork < (1 << 30), "attn_fwd_seqs: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MH_BF16) return mh_attn_fwd_seqs_mfma3(qkv, seq_start, work, nwork, o, lse, M, max_len, H, scale, st);
+  mh_set_error("attn_fwd_seqs: bf16 only (fp32: the uniform entry points, sequence by sequence)");
+  return MH_ERR_ARG;
+}
+
+extern "C" int mh_attn_bwd_seqs(const void* qkv, const void* o, const void* dout, const float* lse, float* scratch, void* dqkv,
+                                const float* rowscale, const int32_t* seq_start, const int32_t* work, int64_t nwork,
+                                int64_t M, int64_t Mpad, int64_t max_len, int H, float scale, const float* cos_t,
+                                const float* sin_t, int dtype, void* stream) {
+  MH_REQUIRE(M > 0 && H > 0 && Mpad >= M && seq_start != nullptr && work != nullptr && nwork > 0 && nwork < (1 << 30) && scratch != nullptr,
+             "attn_bwd_seqs: bad arguments");
+  MH_REQUIRE((cos_t == nullptr) == (sin_t == nullptr), "attn_bwd_seqs: cos and sin tables come together");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MH_BF16)  // (the rotation back rides on the dq / dk stores, at row - seq_start)
+    return mh_attn_bwd_seqs_mfma3(qkv, o, dout, lse, scratch, dqkv, rowscale, seq_start, work, nwork, M, Mpad, max_len, H, scale, cos_t, sin_t, st);
+  mh_set_error("attn_bwd_seqs: bf16 only (fp32: the uniform entry points, sequence by sequence)");
+  return MH_ERR_ARG;
+}

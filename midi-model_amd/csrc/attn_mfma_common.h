@@ -183,3 +183,29 @@ __device__ inline bool attn_work(int& BH, int ntile, int& bh, int& tile) {
   tile = lo + (i - g * n);
   return bh < BH;
 }
+
+// Table form (mh_attn_fwd_seqs / mh_attn_bwd_seqs; kernels in attention_mfma3.hip): the rows of qkv [M, 3D] are n sequences of any
+// length laid end to end and
+// workgroup b takes item b of a work list the HOST built from the lengths (ops.attn_seq_plan): int32 x 4 = sequence (< 0: an
+// empty slot, the list is padded to whole rounds of 8 XCDs), head, tile rank (128 rows, counted from the sequence's FIRST row; rank
+// as in the uniform kernels: 0 is the heaviest tile), and the sequence's first row in the 64-padded statistics scratch of the
+// backward pair ([2][H][Mpad]: every sequence starts on a multiple of 64 there, since the dK/dV kernel stages 64 values at a time
+// with 16-byte requests).  The list carries what attn_work computes: the tiles of one (sequence, head) pair on one XCD (items
+// b, b + 8, ..), heavy tiles first.  Only the kernels' preambles differ: base row, length, clamp, the statistics' offsets.
+struct AttnSeqs {
+  const int* seq_start;  // [n + 1], ascending, seq_start[0] = 0, seq_start[n] = M
+  const int4* work;      // [gridDim.x]
+  int M, Mpad;
+};
+__device__ inline const AttnSeqs& attn_seqs_arg(const AttnSeqs& t) { return t; }  // (the kernels' trailing argument pack)
+__device__ inline bool attn_work_seqs(const AttnSeqs& t, int& start, int& S, int& h, int& tile, int& soff, int item = blockIdx.x) {
+  const int4 w = t.work[item];
+  const int seq = __builtin_amdgcn_readfirstlane(w.x);
+  if (seq < 0) return false;
+  start = __builtin_amdgcn_readfirstlane(t.seq_start[seq]);
+  S = __builtin_amdgcn_readfirstlane(t.seq_start[seq + 1]) - start;
+  h = __builtin_amdgcn_readfirstlane(w.y);
+  tile = __builtin_amdgcn_readfirstlane(w.z);
+  soff = __builtin_amdgcn_readfirstlane(w.w);
+  return true;
+}

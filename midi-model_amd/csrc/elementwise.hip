@@ -1064,10 +1064,13 @@ extern "C" int mh_colsum(float* partial, int64_t nblk, void* out, int D, int acc
 // RoPE, in place on the q and k thirds of qkv[M, 3*H*hd].  Pair (i, i+hd/2); cos/sin tables are fp32
 // and are rounded to the activation dtype before use (the reference casts them, modeling_llama.py:126).
 // ---------------------------------------------------------------------------------------------------
-template <typename T>
+// (POS: mh_rope_pos hands the rows' positions over as ONE trailing argument, int32 [M]; mh_rope's instantiations have none)
+__device__ inline int64_t rope_row_pos(int64_t m, int64_t S, int64_t pos0) { return pos0 + (m % S); }
+__device__ inline int64_t rope_row_pos(int64_t m, int64_t, int64_t, const int* __restrict__ pos) { return pos[m]; }
+template <typename T, typename... POS>
 __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ qkv, const float* __restrict__ cos_t,
                                                    const float* __restrict__ sin_t, int64_t M, int64_t S, int64_t pos0,
-                                                   int H, int hd, float dir) {
+                                                   int H, int hd, float dir, POS... posv) {
   constexpr int N = Pack<T>::N;
   const int half = hd / 2;
   const int cph = half / N;                 // 16-byte chunks per half head
@@ -1081,7 +1084,7 @@ __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ qkv, const fl
     rem /= cph;
     const int h = rem % H;
     const int part = rem / H;  // 0 = q, 1 = k
-    const int64_t pos = pos0 + (m % S);
+    const int64_t pos = rope_row_pos(m, S, pos0, posv...);
     T* p1 = qkv + m * D3 + (int64_t)part * H * hd + (int64_t)h * hd + ch * N;
     T* p2 = p1 + half;
     Pack<T> a = ld16(p1), b = ld16(p2), oa, ob;
@@ -1105,6 +1108,17 @@ extern "C" int mh_rope(void* qkv, const float* cos_t, const float* sin_t, int64_
   const int64_t total = M * 2 * H * (hd / 2 / (dtype == MH_BF16 ? 8 : 4));
   DISPATCH_T(dtype, (rope_kernel<T><<<grid_for(total, 256, 16384), 256, 0, (hipStream_t)stream>>>(
                         (T*)qkv, cos_t, sin_t, M, S, pos0, H, hd, dir >= 0 ? 1.f : -1.f)));
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// mh_rope with row m rotated at pos[m] (packed batches: every sequence restarts at 0).  Same kernel, same roundings.
+extern "C" int mh_rope_pos(void* qkv, const float* cos_t, const float* sin_t, const int32_t* pos, int64_t M, int H, int hd, int dir,
+                           int dtype, void* stream) {
+  MH_REQUIRE(M > 0 && hd % 16 == 0 && pos != nullptr, "rope_pos: bad arguments");
+  const int64_t total = M * 2 * H * (hd / 2 / (dtype == MH_BF16 ? 8 : 4));
+  DISPATCH_T(dtype, (rope_kernel<T, const int*><<<grid_for(total, 256, 16384), 256, 0, (hipStream_t)stream>>>(
+                        (T*)qkv, cos_t, sin_t, M, 1, 0, H, hd, dir >= 0 ? 1.f : -1.f, (const int*)pos)));
   MH_LAUNCH_CHECK();
   return MH_OK;
 }

@@ -13,7 +13,7 @@ row 0 of every sequence the BOS octet, then well-formed events [event_id, params
 from __future__ import annotations
 
 import random
-from typing import List, Sequence, Tuple
+from typing import Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -145,13 +145,43 @@ class WindowSampler:
         self._stage_free.record()
         return out
 
-    def batch(self, indices: Sequence[int], pad_id: int = 0) -> torch.Tensor:
-        """(B, longest window, 8) int64 on the corpus' device: ``collate_fn`` (+ ``augment``) in one launch"""
+    def _draw(self, indices: Sequence[int]):
+        """the batch's RNG draws, in the reference's order -> (windows [(start, length)], augmentation shifts)"""
         shifts, wins = [], []
         for i in indices:
             if self.aug:
                 shifts.append(self.draw_shifts())  # load_midi -> tokenizer.augment draws first (train.py:62-63) ...
             wins.append(self.window(i))            # ... then __getitem__ draws the window (train.py:73-77)
+        return wins, shifts
+
+    def batch(self, indices: Sequence[int], pad_id: int = 0) -> torch.Tensor:
+        """(B, longest window, 8) int64 on the corpus' device: ``collate_fn`` (+ ``augment``) in one launch"""
+        wins, shifts = self._draw(indices)
+        return self._collate(indices, wins, shifts, pad_id)
+
+    def packed_batch(self, indices: Sequence[int], pad_id: int = 0, n_head: Optional[int] = None) -> "PackedBatch":
+        """The windows ``batch(indices)`` would serve -- the same RNG draws in the same order, the same augmentation -- without
+        their padding: ``PackedBatch.from_padded`` of that batch and its windows' lengths (``n_head`` as there)."""
+        wins, shifts = self._draw(indices)
+        return PackedBatch.from_padded(self._collate(indices, wins, shifts, pad_id), [w[1] for w in wins], pad_id, n_head)
+
+    def fill(self, order: Iterable[int], budget_rows: int) -> Iterator[List[int]]:
+        """Cut the index stream ``order`` into batches for ``packed_batch``: indices are taken until the next window would take
+        the batch past ``budget_rows`` rows; that window opens the next batch.  Nothing is cropped and nothing is dropped (a
+        window larger than the budget is a batch of its own).  A window is counted at the most rows it can have -- min(max_len,
+        piece length) - 1, its start is not drawn yet -- so the RNG is untouched and a batch never exceeds the budget."""
+        cur, rows = [], 0
+        for i in order:
+            r = max(min(self.max_len, self.corpus.piece_len(i)) - 1, 0)
+            if cur and rows + r > budget_rows:
+                yield cur
+                cur, rows = [], 0
+            cur.append(i)
+            rows += r
+        if cur:
+            yield cur
+
+    def _collate(self, indices: Sequence[int], wins, shifts, pad_id: int) -> torch.Tensor:
         B = len(wins)
         dev = self.corpus.tokens.device
         cols = np.zeros((9, B), dtype=np.int64)
@@ -166,3 +196,63 @@ class WindowSampler:
             return ops.collate_windows(self.corpus.tokens, d[0], d[1], out, pad_id)
         sh = d[3:9].t().to(torch.int32).contiguous()
         return ops.augment_collate_windows(self.corpus.tokens, d[0], d[1], d[2], sh, self.stats, self.tab, out, pad_id)
+
+
+class PackedBatch:
+    """A training batch without padded events: the windows' rows laid end to end.
+
+    ``x`` / ``y`` [M, 8] int64 (inputs and next-event targets, on the device), ``lengths`` (host) the rows of every sequence in
+    order, ``tail`` how many of the last sequence's rows are padding, ``plan`` the uploaded ops.SeqPlan of the event-level
+    attention.  The plan depends on the net's head count: ``plan_for(n_head, device)`` builds and uploads it on first use (the
+    training step asks with its own head count) and keeps it; ``plan`` is the last one made, None before.  ``from_padded``
+    defines the layout."""
+
+    def __init__(self, x: torch.Tensor, y: torch.Tensor, lengths: Sequence[int], tail: int):
+        self.x, self.y, self.lengths, self.tail = x, y, tuple(lengths), tail
+        self.plan = None
+        self._plans = {}
+
+    def plan_for(self, n_head: int, device=None):
+        """the launch tables of the table-form attention for ``n_head`` heads, on ``device`` (default: where x is): host code plus
+        one non-blocking upload, made once per (head count, device)"""
+        device = torch.device(device if device is not None else self.x.device)
+        key = (int(n_head), device)
+        if key not in self._plans:
+            self._plans[key] = ops.attn_seq_plan(self.lengths, int(n_head)).upload(device)
+        self.plan = self._plans[key]
+        return self.plan
+
+    @property
+    def real_rows(self) -> int:
+        return self.x.shape[0] - self.tail
+
+    @classmethod
+    def from_padded(cls, batch: torch.Tensor, lengths: Sequence[int], pad_id: int = 0, n_head: Optional[int] = None) -> "PackedBatch":
+        """``batch`` (B, L + 1, 8) as ``WindowSampler.batch`` / the reference's collate_fn make it, ``lengths[i]`` the events of
+        window i (the rest of its row is padding).  Window i contributes the rows x = w[:-1], y = w[1:]: lengths[i] - 1 of them,
+        none for a window of one event -- exactly the positions of the padded batch whose targets are not all ignore_index.  M is
+        brought to a multiple of 64 by a LAST sequence of pad events (x = y = pad): a sequence like any other, so every row of
+        every activation is written and finite; its targets are ignored and nothing attends to it, so it adds nothing to the
+        loss or to any gradient.  ``n_head``: make the attention's plan now (plan_for) rather than in the first step."""
+        B, L1, T = batch.shape
+        lengths = [int(n) for n in lengths]
+        assert len(lengths) == B and all(1 <= n <= L1 for n in lengths)
+        rows = [n - 1 for n in lengths if n > 1]
+        real = sum(rows)
+        M = max(64, (real + 63) // 64 * 64)
+        tail = M - real
+        b_idx = np.concatenate([np.full(n - 1, i, dtype=np.int64) for i, n in enumerate(lengths)] + [np.zeros(0, dtype=np.int64)])
+        j_idx = np.concatenate([np.arange(n - 1, dtype=np.int64) for n in lengths] + [np.zeros(0, dtype=np.int64)])
+        idx = torch.from_numpy(np.stack([b_idx, j_idx]))
+        dev = batch.device
+        if dev.type == "cuda":
+            idx = idx.pin_memory().to(dev, non_blocking=True)
+        x = torch.full((M, T), pad_id, dtype=torch.int64, device=dev)
+        y = torch.full((M, T), pad_id, dtype=torch.int64, device=dev)
+        x[:real] = batch[idx[0], idx[1]]
+        y[:real] = batch[idx[0], idx[1] + 1]
+        seq = rows + ([tail] if tail else [])
+        pb = cls(x, y, seq, tail)
+        if n_head is not None:
+            pb.plan_for(n_head)
+        return pb

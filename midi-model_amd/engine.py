@@ -131,6 +131,7 @@ class StackSaved(NamedTuple):
     slen: int
     folded: Optional[list]               # the folded weights the forward ran with; None: the plain blocks
     first: Optional[tokfirst.TokFirst] = None   # layers[0] is tok_first_forward's (x = [hidden ; E ; E], qkv = its projection)
+    seqs: Optional[object] = None               # packed batch: the ops.SeqPlan the forward ran with (nseq / slen are then unused)
 
 
 def _norm_qkv(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, slen: int, rope: RopeTable, pos0: int, rope_in_attn: bool,
@@ -149,6 +150,16 @@ def _norm_qkv(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, slen: int, rop
         if not rope_in_attn:
             ops.rope_(qkv, rope.cos, rope.sin, slen, pos0, spec.H, spec.hd, +1)
     return h1, rstd1, qkv
+
+
+def _attn_fwd_seqs(spec: StackSpec, qkv: torch.Tensor, o: torch.Tensor, rope: RopeTable, seqs) -> torch.Tensor:
+    """Packed batch (event-level stack): ``qkv`` comes UNROTATED out of the plain projection -- the tuned GEMM's RoPE epilogue
+    takes positions pos0 + row % slen and is left alone -- so RoPE is a pass of its own at the rows' positions within their
+    sequences, then ONE attention launch over the sequence table.  Returns lse [H, M]."""
+    ops.rope_pos_(qkv, rope.cos, rope.sin, seqs.pos, spec.H, spec.hd, +1)
+    lse = _empty((spec.H * qkv.shape[0],), qkv, torch.float32)
+    ops.attn_fwd_seqs(qkv, o, lse, seqs, spec.H, spec.scale)
+    return lse
 
 
 def _o_mlp(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, o: torch.Tensor, save: bool, stats: bool):
@@ -178,7 +189,7 @@ def _o_mlp(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, o: torch.Tensor, 
 
 
 def layer_forward(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable,
-                  kv_out: Optional[list] = None, save: bool = True, lean: bool = False):
+                  kv_out: Optional[list] = None, save: bool = True, lean: bool = False, seqs=None):
     """One pre-norm LLaMA block (LlamaDecoderLayer.forward, TF:models/llama/modeling_llama.py:295-324) on x [nseq*slen, D]:
     RMSNorm -> q|k|v projection -> RoPE -> causal attention -> o projection + residual -> RMSNorm -> gate|up projection with
     SwiGLU epilogue -> down projection + residual.  7 launches for the event-level stack in bf16, where RoPE rides on the q|k|v
@@ -187,6 +198,7 @@ def layer_forward(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, nseq: int,
     SwiGLU activation ``a`` is not kept -- the backward recomputes it from the
     stored gate|up with mh_swiglu_fwd, bit for bit (the fused epilogue and that kernel share their roundings) -- which takes
     I of the 8 D + 3 I saved elements per row off the activation memory (the 2x-hidden large shape at 16 x 4096 per GPU: 39 GB).
+    ``seqs`` (event-level stack): the rows are a packed batch -- see _attn_fwd_seqs.
     Returns (block output, LayerSaved | None)."""
     M, D = x.shape
     H = spec.H
@@ -194,10 +206,12 @@ def layer_forward(spec: StackSpec, lw: LayerTensors, x: torch.Tensor, nseq: int,
     # there anyway), so qkv stays unrotated -- except for a prefill, whose K rows go to the cache rotated.
     # event-level stack (heads of 64): RoPE rides on the q|k|v projection's epilogue.
     rope_in_attn = spec.kind != "event" and kv_out is None
-    h1, rstd1, qkv = _norm_qkv(spec, lw, x, slen, rope, 0, rope_in_attn, stats=True)
+    h1, rstd1, qkv = _norm_qkv(spec, lw, x, slen, rope, 0, rope_in_attn or seqs is not None, stats=True)
     o = _empty((M, D), x)
     lse = None
-    if spec.kind == "event":
+    if seqs is not None:
+        lse = _attn_fwd_seqs(spec, qkv, o, rope, seqs)
+    elif spec.kind == "event":
         lse = _empty((nseq * H * ops.round_up(slen, 64),), x, torch.float32)
         ops.attn_fwd(qkv, o, lse, nseq, slen, H, spec.scale)
     elif rope_in_attn:
@@ -219,7 +233,7 @@ FOLD_MIN_ROWS_ON_THE_FLY = 131072   # (12 layers: the fold ~0.7 ms of elementwis
 
 def layer_forward_folded(spec: StackSpec, lw: LayerTensors, fold, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable,
                          parts_in: Optional[torch.Tensor], kv_out: Optional[list] = None, saved_out: Optional[list] = None,
-                         lean: bool = False):
+                         lean: bool = False, seqs=None):
     """layer_forward without its two RMSNorm passes (LlamaDecoderLayer.forward, TF:models/llama/modeling_llama.py:295-324;
     LlamaRMSNorm :62-67): ``fold`` = (wqkv * n1, wgu * n2) from fold_norm_weights, so norm(x) W^T = rstd (.) (x W'^T) and the
     normalised activations h1 / h2 are never written, read or kept (training: a fifth of the saved activations less per layer).
@@ -244,7 +258,10 @@ def layer_forward_folded(spec: StackSpec, lw: LayerTensors, fold, x: torch.Tenso
     qkv = _empty((M, 3 * D), x)
     o = _empty((M, D), x)
     lse = None
-    if spec.kind == "event":
+    if seqs is not None:   # packed batch: the plain scaled projection, then _attn_fwd_seqs
+        ops.gemm_nt_scaled(x, wq_n, qkv, rstd1)
+        lse = _attn_fwd_seqs(spec, qkv, o, rope, seqs)
+    elif spec.kind == "event":
         ops.gemm_rope(x, wq_n, qkv, rope.fused(), slen, 0, spec.hd, rowscale=rstd1)
         lse = _empty((nseq * H * ops.round_up(slen, 64),), x, torch.float32)
         ops.attn_fwd(qkv, o, lse, nseq, slen, H, spec.scale)
@@ -336,7 +353,7 @@ def runs_folded(spec: StackSpec, x: torch.Tensor, save: bool, kv_out: Optional[l
 
 
 def layer_backward(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, keep: LayerSaved, dx: torch.Tensor, nseq: int, slen: int,
-                   rope: RopeTable, accumulate: bool) -> torch.Tensor:
+                   rope: RopeTable, accumulate: bool, seqs=None) -> torch.Tensor:
     """The backward of layer_forward: dx = d loss / d block output -> d loss / d block input (written over ``dx``), the layer's
     parameter gradients to ``lg``."""
     M, D = dx.shape
@@ -367,7 +384,9 @@ def layer_backward(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, keep: La
     ops.gemm_nt(dx2, lw.wo, do, tb=True)            # d o = dx2 @ wo
     linear_wgrad(dx2, keep.o, lg.wo, accumulate)
     dqkv = _empty((M, 3 * D), dx)
-    if spec.kind == "event":
+    if seqs is not None:  # (packed batch: rotated back in the stores at row - start of its sequence)
+        ops.attn_bwd_seqs(keep.qkv, keep.o, do, keep.lse, dqkv, seqs, H, spec.scale, rope.cos, rope.sin)
+    elif spec.kind == "event":
         ops.attn_bwd(keep.qkv, keep.o, do, keep.lse, dqkv, nseq, slen, H, spec.scale, rope.cos, rope.sin)  # (rotated back in the stores)
     else:  # (saved qkv is unrotated: the forward ran with save=True, never as a prefill)
         ops.tokattn_bwd(keep.qkv, do, dqkv, nseq, slen, H, spec.scale, rope.cos, rope.sin)
@@ -380,7 +399,7 @@ def layer_backward(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, keep: La
 
 
 def layer_backward_folded(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, fold, keep: LayerSaved, dx: torch.Tensor, nseq: int,
-                          slen: int, rope: RopeTable, accumulate: bool) -> torch.Tensor:
+                          slen: int, rope: RopeTable, accumulate: bool, seqs=None) -> torch.Tensor:
     """The backward of layer_forward_folded.  With z = x W'^T, y = rstd (.) z: the producers of d y store d z = rstd (.) d y
     (the SwiGLU-backward epilogue, the attention backward's stores), t = d z W' is the dgrad on the folded weights,
     dx = t - x (rstd^2 / D) rowdot(t, x) + dres the norm's backward without its weight, and the weight gradient G' = d z^T x
@@ -390,7 +409,9 @@ def layer_backward_folded(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, f
     wq_n, wgu_n = fold
     dx2, do = _folded_mlp_o_backward(spec, lw, lg, wgu_n, keep, dx, accumulate)
     dz1 = _empty((M, 3 * D), dx)
-    if spec.kind == "event":
+    if seqs is not None:
+        ops.attn_bwd_seqs(keep.qkv, keep.o, do, keep.lse, dz1, seqs, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
+    elif spec.kind == "event":
         ops.attn_bwd(keep.qkv, keep.o, do, keep.lse, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
     else:
         ops.tokattn_bwd(keep.qkv, do, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
@@ -483,7 +504,7 @@ def tok_first_backward(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, fold
 
 def stack_forward(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable,
                   save: bool, kv_out: Optional[list] = None, lean: bool = False, folded=None,
-                  first: Optional[tokfirst.TokFirst] = None):
+                  first: Optional[tokfirst.TokFirst] = None, seqs=None):
     """x [nseq*slen, D] (inputs_embeds) -> (last_hidden_state [nseq*slen, D], StackSaved | None).
     save=True keeps what the backward needs (``lean``: minus the SwiGLU activations, recomputed in the backward);
     kv_out (prefill) receives each layer's post-RoPE qkv.  runs_folded picks the blocks: plain (layer_forward) or with the
@@ -491,11 +512,17 @@ def stack_forward(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, 
     MIDIModel.folded_weights, re-derived after every update -- the training forward takes no other, and the backward finds them
     in the context); a forward-only pass without one makes the fold here, from the live weights, per call.
     ``first`` (token-level stack, training): what the rows ``x`` were laid out from; where the folded training blocks run and
-    tokfirst.table_first_ok holds, the first block takes tok_first_forward and stack_backward returns TokFirstGrads."""
+    tokfirst.table_first_ok holds, the first block takes tok_first_forward and stack_backward returns TokFirstGrads.
+    ``seqs`` (event-level stack, training / validation): an uploaded ops.SeqPlan -- the rows are a PACKED batch, sequences of any
+    lengths laid end to end (data.PackedBatch); ``nseq`` / ``slen`` are then 1 / M and only the attention and RoPE see the table."""
     _check_heads(spec)
     M, D = x.shape
     assert M == nseq * slen
-    rope.ensure(slen)
+    if seqs is not None:
+        assert spec.kind == "event" and kv_out is None and first is None and seqs.M == M and seqs.H == spec.H
+        rope.ensure(seqs.max_len)
+    else:
+        rope.ensure(slen)
     if runs_folded(spec, x, save, kv_out, folded is not None):
         if folded is None:
             folded = fold_norm_weights(W)
@@ -509,16 +536,16 @@ def stack_forward(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, 
         if first is not None and li == 0:
             x, parts = tok_first_forward(spec, lw, folded[li], first, x, nseq, rope, saved, lean)
         elif folded is not None:
-            x, parts = layer_forward_folded(spec, lw, folded[li], x, nseq, slen, rope, parts, kv_out, saved, lean)
+            x, parts = layer_forward_folded(spec, lw, folded[li], x, nseq, slen, rope, parts, kv_out, saved, lean, seqs)
         else:
-            x, keep = layer_forward(spec, lw, x, nseq, slen, rope, kv_out, save, lean and save)
+            x, keep = layer_forward(spec, lw, x, nseq, slen, rope, kv_out, save, lean and save, seqs)
             if save:
                 saved.append(keep)
     y = _empty((M, D), x)
     # (the forward-only folded pass is the one form that asks the final norm for no rstd)
     rstdf = _empty((M,), x, torch.float32) if save or folded is None else None
     ops.rmsnorm_fwd(x, W.norm, y, rstdf, spec.eps)
-    return y, (StackSaved(saved, x, rstdf, nseq, slen, folded, first) if save else None)
+    return y, (StackSaved(saved, x, rstdf, nseq, slen, folded, first, seqs) if save else None)
 
 
 def stack_backward(spec: StackSpec, W: StackTensors, G: StackTensors, ctx: StackSaved, dy: torch.Tensor,
@@ -536,9 +563,9 @@ def stack_backward(spec: StackSpec, W: StackTensors, G: StackTensors, ctx: Stack
         if ctx.first is not None and li == 0:
             dx = tok_first_backward(spec, lw, lg, ctx.folded[li], ctx.layers[li], ctx.first, dx, ctx.nseq, rope, accumulate)
         elif ctx.folded is not None:
-            dx = layer_backward_folded(spec, lw, lg, ctx.folded[li], ctx.layers[li], dx, ctx.nseq, ctx.slen, rope, accumulate)
+            dx = layer_backward_folded(spec, lw, lg, ctx.folded[li], ctx.layers[li], dx, ctx.nseq, ctx.slen, rope, accumulate, ctx.seqs)
         else:
-            dx = layer_backward(spec, lw, lg, ctx.layers[li], dx, ctx.nseq, ctx.slen, rope, accumulate)
+            dx = layer_backward(spec, lw, lg, ctx.layers[li], dx, ctx.nseq, ctx.slen, rope, accumulate, ctx.seqs)
         ctx.layers[li] = None                           # activations are released back to front
         if on_layer_done is not None:
             on_layer_done(li)

@@ -586,6 +586,23 @@ def attn_bwd(qkv, o, dout, lse, dqkv, B: int, S: int, H: int, scale: float, cos_
     return dqkv
 
 
+# ------------------------------------------------------------------------- attention, packed batches
+# attn_seq_plan, rope_pos_, attn_fwd_seqs, attn_bwd_seqs (the table form of the event-level attention: one launch per kernel over
+# sequences of any lengths laid end to end) live in ops_packed.py and are resolved here on first use.
+# WHY not plain functions of this module: the CPU emulation of the test suite (tests/emu_ops.py, install()) demands a stand-in of its
+# own for every public callable it finds in dir(ops), and that file predates these entry points; their stand-ins are in
+# tests/emu_packed.py, installed on top of it.  Moving the five functions here needs stand-ins in emu_ops.py in the same change --
+# without them every host test that installs the emulation fails at its completeness check.
+_PACKED = ("SeqPlan", "attn_seq_plan", "rope_pos_", "attn_fwd_seqs", "attn_bwd_seqs")
+
+
+def __getattr__(name: str):
+    if name in _PACKED:
+        from . import ops_packed
+        return getattr(ops_packed, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def tokattn_fwd(qkv, o, N: int, T: int, H: int, scale: float, cos_t=None, sin_t=None):
     """cos_t/sin_t: RoPE fused in (qkv unrotated); see mh_tokattn_fwd"""
     lib().call("mh_tokattn_fwd", _p(qkv), _p(o), N, T, H, scale, _p(cos_t), _p(sin_t), dt(qkv), _stream())

@@ -24,6 +24,7 @@ import torch
 
 from . import engine, mixed, ops, tokfirst
 from .config import MIDIModelConfig
+from .data import PackedBatch
 from .model import MIDIModel
 
 
@@ -575,17 +576,30 @@ class TrainMIDIModel(MIDIModel):
         self._micro = 0
 
     # --------------------------------------------------------------------------------- fused step
-    def _loss_and_backward(self, batch: torch.Tensor, backward: bool, want_acc: bool = False):
-        """train.py:168-188 (+ its backward).  batch (B, S+1, 8) int64.  Returns (loss[1] fp32 device tensor, acc)."""
+    def _loss_and_backward(self, batch, backward: bool, want_acc: bool = False):
+        """train.py:168-188 (+ its backward).  batch (B, S+1, 8) int64, or a data.PackedBatch: the same windows laid end to end
+        without their padding -- one "sequence" of M rows for everything but the event-level attention and RoPE, which take the
+        batch's sequence table (same loss and gradients as the padded batch of those windows: DESIGN.md 7.3).
+        Returns (loss[1] fp32 device tensor, acc)."""
         self._require_gpu()
         if self._lora is not None and self._lora.dirty:
             self._lora.materialize(self)  # live weights <- base + scale * B @ A
         tok = self.tokenizer
         dev, dty = self.device, self.dtype
-        self._check_ids(batch)
-        batch = batch.to(device=dev, dtype=torch.long)
-        x = batch[:, :-1].contiguous()
-        y = batch[:, 1:].contiguous()
+        seqs = None
+        if isinstance(batch, PackedBatch):
+            if self.sample_seq:
+                raise NotImplementedError("sample_seq picks positions of a [B, S] batch: not defined for a PackedBatch")
+            self._check_ids(batch.x)
+            self._check_ids(batch.y)
+            x = batch.x.to(device=dev, dtype=torch.long).unsqueeze(0).contiguous()
+            y = batch.y.to(device=dev, dtype=torch.long).unsqueeze(0).contiguous()
+            seqs = batch.plan_for(self._specs["net"].H, dev)
+        else:
+            self._check_ids(batch)
+            batch = batch.to(device=dev, dtype=torch.long)
+            x = batch[:, :-1].contiguous()
+            y = batch[:, 1:].contiguous()
         B, S, T = x.shape
         spec, tspec = self._specs["net"], self._specs["net_token"]
         Wn, Wt = self._W["net"], self._W["net_token"]
@@ -597,7 +611,7 @@ class TrainMIDIModel(MIDIModel):
         e = torch.empty((M, D), dtype=dty, device=dev)
         ops.embed_sum_fwd(x.view(M, T), Wn.embed, e)
         hidden, ctx_net = engine.stack_forward(spec, Wn, e, B, S, self.rope("net"), save=backward, lean=self.lean_activations,
-                                               folded=self._train_fold(spec, e, backward))
+                                               folded=self._train_fold(spec, e, backward), seqs=seqs)
         del e
         sel = None
         if self.sample_seq:  # train.py:172-175: keep the last position + up to 127 random others
