@@ -385,6 +385,19 @@ int mh_attn_decode(const void* qkv, const void* kcache, const void* vcache, void
 int mh_attn_decode_append(const void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache, void* o,
                           int64_t B, int H, int hd, int64_t Lmax, int64_t pos, float scale, const int32_t* pos_dev,
                           int dtype, void* stream);
+/* The per-row forms (MIDIModel.generate_ragged: B prompts of B lengths in one decode batch): sequence b does what the uniform
+ * entry point does at pos = row_pos[b] -- RoPE there, K/V stored at cache row row_pos[b], attention over rows [0, row_pos[b]].
+ * row_pos is a DEVICE int32 [B] and is always read on the device (one scalar load per workgroup); it must not be NULL.  bf16 and
+ * fp32, hd == 64 only, B < 65536, Lmax < 2^24; anything else is MH_ERR_ARG.  A position at or past Lmax: mh_kv_append_rows
+ * writes nothing for that row, the attention forms clamp to row Lmax - 1 (as the uniform kernels do with *pos_dev).  The same
+ * kernels as the uniform entry points (a template parameter), the same arithmetic in the same order.                          */
+int mh_kv_append_rows(void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache, int64_t B, int H, int hd,
+                      int64_t Lmax, const int32_t* row_pos, int dtype, void* stream);
+int mh_attn_decode_rows(const void* qkv, const void* kcache, const void* vcache, void* o, int64_t B, int H, int hd,
+                        int64_t Lmax, float scale, const int32_t* row_pos, int dtype, void* stream);
+int mh_attn_decode_append_rows(const void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache, void* o,
+                               int64_t B, int H, int hd, int64_t Lmax, float scale, const int32_t* row_pos, int dtype,
+                               void* stream);
 /* Decode over a prompt that every row of the batch shares (MIDIModel.generate(share_prompt=True)); head_dim 64 only.
  * The prompt's K/V are cached once, kpre / vpre [H, Pmax, hd] (rows [0, pre_len) valid); each row keeps only its own suffix,
  * ksuf / vsuf [B, H, Lsuf, hd].  qkv [B, 3*H*hd] holds the UNROTATED q,k,v of absolute position `pos` and is left untouched.
@@ -421,6 +434,14 @@ int mh_attn_fwd_tail(const void* qkv, void* o, float* lse, int64_t B, int64_t S,
 /* copy rotated K and V of a prefill (qkv[B*S,3*H*hd]) into the cache rows [0,S).                           */
 int mh_kv_store_prefill(const void* qkv, void* kcache, void* vcache, int64_t B, int64_t S, int H, int hd,
                         int64_t Lmax, int dtype, void* stream);
+
+/* The K/V store of a PACKED prefill: qkv [M, 3*H*hd] holds n sequences laid end to end, seq_start device int32 [n + 1]
+ * (mh_attn_fwd_seqs' table); packed row m of sequence s goes to cache row m - seq_start[s] of (s, h) in k,v [n,H,Lmax,hd], and no
+ * other cache row is written.  16 bytes per lane: hd % 8 == 0.  Every length must be <= Lmax: the host refuses M > n * Lmax, the
+ * caller (midi_model_amd.ops.kv_store_seqs) checks the lengths it built the table from, and the kernel drops a row at or past
+ * Lmax instead of writing it.                                                                                               */
+int mh_kv_store_seqs(const void* qkv, const int32_t* seq_start, void* kcache, void* vcache, int64_t n, int64_t M, int H, int hd,
+                     int64_t Lmax, int dtype, void* stream);
 
 /* ---- grammar-masked softmax for the sampler (midi_model.py:202-223) -----------------------------------------
  * probs[b,:] = softmax(logits[b,:]/temp) * mask_b, mask_b = ids in [lo[b],hi[b]) or, when lo[b] < 0, the

@@ -478,20 +478,27 @@ extern "C" int mh_tokattn_bwd_rows(const void* zc, const int64_t* ids, int64_t l
 // ---------------------------------------------------------------------------------------------------
 // decode: KV cache [B,H,Lmax,HD]; append (with RoPE of q,k) and single-query attention
 // ---------------------------------------------------------------------------------------------------
-template <typename T>
+// ROWS (generate_ragged): every sequence sits at a position of its own, pos_dev[b] (device int32 [B]).  The grid is then
+// (blocks over one sequence's H * hd/2 pairs, B): blockIdx.y is the sequence, so the position is one scalar load per workgroup.
+template <typename T, bool ROWS = false>
 __global__ __launch_bounds__(256) void kv_append_kernel(T* __restrict__ qkv, const float* __restrict__ cos_t,
                                                         const float* __restrict__ sin_t, T* __restrict__ kc,
                                                         T* __restrict__ vc, int64_t B, int H, int hd, int64_t Lmax,
                                                         int64_t pos, const int32_t* __restrict__ pos_dev) {
   // one thread per (b, h, pair index i < hd/2): rotate q and k, store k and v rows
-  if (pos_dev != nullptr) pos = *pos_dev;  // graph replay: the position lives in device memory
+  if constexpr (ROWS) {
+    pos = pos_dev[blockIdx.y];
+    if (pos < 0) return;
+  } else {
+    if (pos_dev != nullptr) pos = *pos_dev;  // graph replay: the position lives in device memory
+  }
   if (pos >= Lmax) return;
   const int half = hd / 2;
-  const int64_t total = B * H * half;
+  const int64_t total = ROWS ? (int64_t)H * half : B * H * half;
   const int64_t D = (int64_t)H * hd;
   for (int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x; it < total; it += (int64_t)gridDim.x * 256) {
     const int i = (int)(it % half);
-    const int64_t bh = it / half;
+    const int64_t bh = ROWS ? (int64_t)blockIdx.y * H + it / half : it / half;
     const int h = (int)(bh % H);
     const int64_t b = bh / H;
     const float c = rnd<T>(cos_t[pos * half + i]), s = rnd<T>(sin_t[pos * half + i]);
@@ -519,6 +526,28 @@ extern "C" int mh_kv_append(void* qkv, const float* cos_t, const float* sin_t, v
   const int64_t total = B * H * (hd / 2);
   DISPATCH_T(dtype, (kv_append_kernel<T><<<(int)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
                         (T*)qkv, cos_t, sin_t, (T*)kcache, (T*)vcache, B, H, hd, Lmax, pos, pos_dev)));
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// the head_dim / dtype / pointer checks the three per-row entry points share
+#define MH_REQUIRE_ROWS(name)                                                                                          \
+  do {                                                                                                                 \
+    MH_REQUIRE(hd == 64, name ": head_dim %d unsupported (64)", hd);                                                   \
+    MH_REQUIRE(dtype == MH_BF16 || dtype == MH_F32, name ": bad dtype %d", dtype);                                     \
+    MH_REQUIRE(row_pos != nullptr, name ": row_pos is NULL (one device int32 position per sequence)");                 \
+    MH_REQUIRE(B > 0 && B < 65536 && H > 0 && Lmax > 0 && Lmax < (1 << 24), name ": bad args B=%ld H=%d Lmax=%ld",     \
+               (long)B, H, (long)Lmax);                                                                                \
+  } while (0)
+
+extern "C" int mh_kv_append_rows(void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache, int64_t B,
+                                 int H, int hd, int64_t Lmax, const int32_t* row_pos, int dtype, void* stream) {
+  MH_REQUIRE_ROWS("kv_append_rows");
+  MH_REQUIRE(qkv != nullptr && cos_t != nullptr && sin_t != nullptr && kcache != nullptr && vcache != nullptr,
+             "kv_append_rows: null buffer");
+  const dim3 grid((unsigned)((H * (hd / 2) + 255) / 256), (unsigned)B);
+  DISPATCH_T(dtype, (kv_append_kernel<T, true><<<grid, 256, 0, (hipStream_t)stream>>>((T*)qkv, cos_t, sin_t, (T*)kcache,
+                                                                                      (T*)vcache, B, H, hd, Lmax, 0, row_pos)));
   MH_LAUNCH_CHECK();
   return MH_OK;
 }
@@ -559,6 +588,54 @@ extern "C" int mh_kv_store_rows(const void* qkv, void* kcache, void* vcache, int
 extern "C" int mh_kv_store_prefill(const void* qkv, void* kcache, void* vcache, int64_t B, int64_t S, int H, int hd,
                                    int64_t Lmax, int dtype, void* stream) {
   return mh_kv_store_rows(qkv, kcache, vcache, B, S, H, hd, Lmax, 0, dtype, stream);
+}
+
+// Packed prefill (generate_ragged): row m of qkv [M, 3 H hd] belongs to the sequence s with seq_start[s] <= m < seq_start[s + 1]
+// and goes to cache row m - seq_start[s] of (s, h).  One lane per 16 bytes of a K row and of a V row; the sequence is found by
+// bisection of the (L2-resident, n + 1 entries) table.  A row at or past Lmax is dropped, never written.
+template <typename T>
+__global__ __launch_bounds__(256) void kv_store_seqs_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ seq_start,
+                                                            T* __restrict__ kc, T* __restrict__ vc, int n, int64_t M, int H,
+                                                            int hd, int64_t Lmax) {
+  constexpr int N = Pack<T>::N;
+  const int cph = hd / N;
+  const int64_t total = M * H * cph;
+  const int64_t D = (int64_t)H * hd;
+  const int64_t it = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (it >= total) return;
+  const int c = (int)(it % cph);
+  const int64_t r = it / cph;
+  const int h = (int)(r % H);
+  const int64_t m = r / H;
+  int lo = 0, hi = n;  // seq_start[lo] <= m < seq_start[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int64_t)seq_start[mid] <= m) lo = mid; else hi = mid;
+  }
+  const int64_t row = m - seq_start[lo];
+  if (row < 0 || row >= Lmax) return;
+  const T* src = qkv + m * 3 * D + (int64_t)h * hd + c * N;
+  const int64_t dst = (((int64_t)lo * H + h) * Lmax + row) * hd + c * N;
+  st16(kc + dst, ld16(src + D));
+  st16(vc + dst, ld16(src + 2 * D));
+}
+
+// (the table lives in device memory: the host refuses what it can see -- M rows cannot fit n sequences of at most Lmax rows --
+//  and the kernel drops any row at or past Lmax; ops.kv_store_seqs checks the plan's host copy of the lengths before the call)
+extern "C" int mh_kv_store_seqs(const void* qkv, const int32_t* seq_start, void* kcache, void* vcache, int64_t n, int64_t M, int H,
+                                int hd, int64_t Lmax, int dtype, void* stream) {
+  MH_REQUIRE(qkv != nullptr && seq_start != nullptr && kcache != nullptr && vcache != nullptr, "kv_store_seqs: null buffer");
+  MH_REQUIRE(dtype == MH_BF16 || dtype == MH_F32, "kv_store_seqs: bad dtype %d", dtype);
+  MH_REQUIRE(n > 0 && n < (1 << 30) && M >= n && M < (1ll << 31) && H > 0 && hd > 0 && hd % 8 == 0 && Lmax > 0,
+             "kv_store_seqs: bad args n=%ld M=%ld H=%d hd=%d Lmax=%ld", (long)n, (long)M, H, hd, (long)Lmax);
+  MH_REQUIRE(M <= n * Lmax, "kv_store_seqs: %ld rows in %ld sequences: a length exceeds Lmax=%ld", (long)M, (long)n, (long)Lmax);
+  const int64_t total = M * H * (hd / (dtype == MH_BF16 ? 8 : 4));
+  const int64_t g = (total + 255) / 256;
+  MH_REQUIRE(g < (1ll << 31), "kv_store_seqs: %ld workgroups", (long)g);
+  DISPATCH_T(dtype, (kv_store_seqs_kernel<T><<<(unsigned)g, 256, 0, (hipStream_t)stream>>>((const T*)qkv, seq_start, (T*)kcache,
+                                                                                           (T*)vcache, (int)n, M, H, hd, Lmax)));
+  MH_LAUNCH_CHECK();
+  return MH_OK;
 }
 
 // cache rows [0, n) of every (sequence, head) back into the K and V columns of rows [b * Stot, b * Stot + n) of a fused
@@ -631,7 +708,9 @@ __device__ inline float group_sum(float v) {
 // new row goes to suffix row pos - pre_len, the key loop covers suffix rows [0, pos - pre_len], and before normalising the
 // block adds the ceil(pre_len / chunk) partials (acc[HD], m, l) that mh_attn_prefix_partial left for its (b, h), in chunk order.
 // The trailing arguments are read by SHARED instantiations only.
-template <typename T, int HD, bool APPEND, bool SHARED = false>
+// ROWS (generate_ragged; not with SHARED): sequence b sits at a position of its own, pos_dev[b] (device int32 [B]).  The grid is
+// (H, B) -- blockIdx.y is the sequence -- so the position is one scalar load per workgroup, issued with the argument fetch.
+template <typename T, int HD, bool APPEND, bool SHARED = false, bool ROWS = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ qkv, T* kc, T* vc, T* __restrict__ o, int H,
                                                           int64_t Lmax, int64_t len, float scale,
                                                           const int32_t* __restrict__ pos_dev,
@@ -640,11 +719,17 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
                                                           int pre_len = 0, const int32_t* __restrict__ pre_len_dev = nullptr,
                                                           int64_t n_bh = 0) {
   static_assert(!SHARED || APPEND, "the shared-prefix form appends");
+  static_assert(!ROWS || !SHARED, "per-row positions: the plain cache only");
   // every kernel argument fetched at entry in one batch (hipcc sinks each s_load into the block that first uses it otherwise:
   // a scalar-cache miss + wait per block on a kernel whose whole run is a few microseconds)
   asm volatile("" ::"s"(qkv), "s"(kc), "s"(vc), "s"(o), "s"(H), "s"(Lmax), "s"(len), "s"(scale));
   asm volatile("" ::"s"(pos_dev), "s"(cos_t), "s"(sin_t));
-  if (pos_dev != nullptr) len = (int64_t)*pos_dev + 1;  // graph replay: attend to rows [0, pos]
+  if constexpr (ROWS) {
+    len = (int64_t)pos_dev[blockIdx.y] + 1;  // this sequence's position
+    if (len < 1) len = 1;
+  } else {
+    if (pos_dev != nullptr) len = (int64_t)*pos_dev + 1;  // graph replay: attend to rows [0, pos]
+  }
   int64_t rpos = len - 1;  // the position RoPE runs at
   if constexpr (SHARED) {
     if (pre_len_dev != nullptr) pre_len = *pre_len_dev;
@@ -661,9 +746,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
   // reading its own stores back through L2 (r04: a write -> read round trip on the critical path of every decode attention launch)
   __shared__ __attribute__((aligned(16))) T sh_kn[APPEND ? HD : 8], sh_vn[APPEND ? HD : 8];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t bh = blockIdx.x;
-  const int64_t b = bh / H;
-  const int h = (int)(bh - b * H);
+  const int64_t bh = ROWS ? (int64_t)blockIdx.y * H + blockIdx.x : (int64_t)blockIdx.x;
+  const int64_t b = ROWS ? (int64_t)blockIdx.y : bh / H;
+  const int h = ROWS ? (int)blockIdx.x : (int)(bh - b * H);
   const int64_t D = (int64_t)H * HD;
   const int ch = lane % LPK, grp = lane / LPK;
   const T* qrow = qkv + b * 3 * D + (int64_t)h * HD;
@@ -877,6 +962,40 @@ extern "C" int mh_attn_decode_append(const void* qkv, const float* cos_t, const 
                                      const int32_t* pos_dev, int dtype, void* stream) {
   MH_REQUIRE(cos_t != nullptr && sin_t != nullptr, "attn_decode_append: needs the rope tables");
   return attn_decode_launch(qkv, cos_t, sin_t, kcache, vcache, o, B, H, hd, Lmax, pos + 1, scale, pos_dev, dtype, stream);
+}
+
+// The per-row forms: sequence b at position row_pos[b] (device int32 [B], always read on the device).  bf16 / fp32, head_dim 64.
+static int attn_decode_rows_launch(const void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache, void* o,
+                                   int64_t B, int H, int64_t Lmax, float scale, const int32_t* row_pos, int dtype, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)H, (unsigned)B);
+#define LAUNCH_DEC_ROWS(TT, APP)                                                                                           \
+  attn_decode_kernel<TT, 64, APP, false, true><<<grid, 256, 0, st>>>((const TT*)qkv, (TT*)kcache, (TT*)vcache, (TT*)o, H, Lmax, \
+                                                                     0, scale, row_pos, cos_t, sin_t)
+  if (dtype == MH_BF16) {
+    if (cos_t != nullptr) LAUNCH_DEC_ROWS(bf16, true); else LAUNCH_DEC_ROWS(bf16, false);
+  } else {
+    if (cos_t != nullptr) LAUNCH_DEC_ROWS(float, true); else LAUNCH_DEC_ROWS(float, false);
+  }
+#undef LAUNCH_DEC_ROWS
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+extern "C" int mh_attn_decode_rows(const void* qkv, const void* kcache, const void* vcache, void* o, int64_t B, int H, int hd,
+                                   int64_t Lmax, float scale, const int32_t* row_pos, int dtype, void* stream) {
+  MH_REQUIRE_ROWS("attn_decode_rows");
+  MH_REQUIRE(qkv != nullptr && kcache != nullptr && vcache != nullptr && o != nullptr, "attn_decode_rows: null buffer");
+  return attn_decode_rows_launch(qkv, nullptr, nullptr, (void*)kcache, (void*)vcache, o, B, H, Lmax, scale, row_pos, dtype, stream);
+}
+
+extern "C" int mh_attn_decode_append_rows(const void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache,
+                                          void* o, int64_t B, int H, int hd, int64_t Lmax, float scale, const int32_t* row_pos,
+                                          int dtype, void* stream) {
+  MH_REQUIRE_ROWS("attn_decode_append_rows");
+  MH_REQUIRE(qkv != nullptr && cos_t != nullptr && sin_t != nullptr && kcache != nullptr && vcache != nullptr && o != nullptr,
+             "attn_decode_append_rows: null buffer (the rope tables are needed: qkv arrives unrotated)");
+  return attn_decode_rows_launch(qkv, cos_t, sin_t, kcache, vcache, o, B, H, Lmax, scale, row_pos, dtype, stream);
 }
 
 // The suffix half of decode attention over a shared prompt (attention_shared.hip holds the prefix half and the layout of `ws`).

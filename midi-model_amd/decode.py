@@ -28,6 +28,13 @@ is keyed by (parameter buffer, batch, capacity, temperature, top_p, top_k); ``MI
 shared_capacity rows) holds the prompt's K/V, ``kv1`` only the generated suffix, a device int32 ``pre_len`` sits beside ``pos``,
 and the net step's attention is the two launches of shared.py.  The captured graph reads ``pos`` and ``pre_len`` from device
 memory and its launch geometry depends on the capacities only, so one session serves every prompt length <= shared_capacity.
+
+``ragged`` (generate_ragged): the B rows continue B DIFFERENT prompts of B different lengths, in lockstep.  ``pos`` is then int32 [B]
+-- every row's own position -- the net step's attention runs the per-row kernels on it (engine.stack_decode(row_pos=...)), and
+the net body advances it on the device as pos = min(pos + 1, pos_limit), pos_limit = the call's max_len: a row that has reached
+max_len is PARKED there, keeps overwriting cache row max_len (capacity max_len + 1, the plain rule) and keeps being sampled; the
+host drops what it samples.  No per-row host state, no extra sync; the graphs' geometry depends on B and the capacity only, so
+one pooled session serves any mix of lengths.  The token level, the sampler and the noise graph are row-uniform and unchanged.
 """
 from __future__ import annotations
 
@@ -58,12 +65,14 @@ def graphs_enabled(device: torch.device) -> bool:
 
 
 class DecodeSession:
-    def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int, shared_capacity: int = 0):
+    def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int, shared_capacity: int = 0,
+                 ragged: bool = False):
         tok = model.tokenizer
         self.model, self.B, self.cap, self.temp = model, B, capacity, float(temp)
         self.top_p, self.top_k = float(top_p), int(top_k)
         self.shared_capacity = int(shared_capacity)
-        self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity)
+        self.ragged = bool(ragged)
+        self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged)
         dev, dt = model.device, model.dtype
         self.T, self.V, self.Vp = tok.max_token_seq, tok.vocab_size, model.vocab_padded
         spec, tspec = model._specs["net"], model._specs["net_token"]
@@ -85,7 +94,9 @@ class DecodeSession:
         self.first_span, self.max_range = ops.mask_spans(first, lo, hi)  # (generate() only ever clears bits of first_mask)
         self.fused_sampler = (1 <= self.top_k <= min(ops.SAMPLE_MAX_K, self.V) and max(self.max_range) <= ops.SAMPLE_MAX_RANGE
                               and self.first_span[1] - self.first_span[0] <= ops.SAMPLE_MAX_RANGE)
-        self.pos = torch.zeros(1, dtype=torch.int32, device=dev)           # cached events so far (device side)
+        # cached events so far (device side); ragged: per row, and the position a row is parked at (the call's max_len)
+        self.pos = torch.zeros(B if self.ragged else 1, dtype=torch.int32, device=dev)
+        self.pos_limit = torch.zeros(1, dtype=torch.int32, device=dev) if self.ragged else None
         self.hidden = torch.zeros((B, spec.D), dtype=dt, device=dev)
         self.seq = torch.zeros((B, self.T), dtype=torch.long, device=dev)  # tokens of the event being sampled
         self.samples_in = torch.zeros((B,), dtype=torch.long, device=dev)  # token sampled at the previous position
@@ -123,8 +134,12 @@ class DecodeSession:
             self._capture()
 
     @staticmethod
-    def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0):
+    def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False):
+        if ragged and shared_capacity:
+            raise ValueError("DecodeSession: ragged rows have prompts of their own -- not together with a shared prompt")
         key = (model._flat.data_ptr(), model._flat.dtype, B, capacity, float(temp), float(top_p), int(top_k))
+        if ragged:
+            return key + (("ragged",),)
         return key + (("shared", int(shared_capacity)),) if shared_capacity else key
 
     def refresh(self) -> None:
@@ -146,6 +161,11 @@ class DecodeSession:
         spec = m._specs["net"]
         e = torch.empty((self.B, spec.D), dtype=m.dtype, device=m.device)
         ops.embed_sum_fwd(self.seq, m._W["net"].embed, e)  # the event sampled last
+        if self.ragged:  # every row at its own position; a row at pos_limit stays there
+            engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, folded=self.fold1, out=self.hidden, row_pos=self.pos)
+            self.pos.add_(1)
+            torch.minimum(self.pos, self.pos_limit, out=self.pos)
+            return
         sh = None
         if self.kvp is not None:
             from .shared import SharedPrefix
@@ -265,6 +285,8 @@ class DecodeSession:
         self.kv1.len = 0
         self.kv2.len = 0
         self.pos.zero_()
+        if self.pos_limit is not None:
+            self.pos_limit.zero_()
         if self.kvp is not None:
             self.kvp.len = 0
             self.pre_len.zero_()
@@ -294,6 +316,31 @@ class DecodeSession:
         y = engine.stack_prefill(spec, m._W["net"], e, B, S, self.rope1, self.kv1, folded=self.fold1)
         self.hidden.copy_(y.view(B, S, spec.D)[:, -1])
         self.pos.fill_(S)
+
+    def set_limit(self, max_len: int) -> None:
+        """(ragged) the position rows are parked at, for this call: cache row max_len must exist"""
+        if max_len + 1 > self.cap:
+            raise ValueError(f"max_len {max_len} in a ragged session of capacity {self.cap} (max_len + 1 rows are needed)")
+        self.pos_limit.fill_(max_len)
+
+    def prefill_ragged(self, tokens: torch.Tensor, lengths) -> None:
+        """tokens [M, T]: the B prompts laid end to end, prompt b of lengths[b] events.  One packed causal forward from empty
+        caches (engine.stack_prefill_seqs); leaves hidden[b] = prompt b's last position and pos[b] = lengths[b]."""
+        m = self.model
+        spec = m._specs["net"]
+        lengths = [int(n) for n in lengths]
+        M, T = tokens.shape
+        if not self.ragged or len(lengths) != self.B or min(lengths) < 1 or sum(lengths) != M:
+            raise ValueError(f"prefill_ragged: {len(lengths)} lengths summing to {sum(lengths)} for {M} rows in a session of "
+                             f"{self.B} rows (ragged: {self.ragged})")
+        if max(lengths) >= self.cap:
+            raise ValueError(f"prompt of {max(lengths)} events in a ragged session of capacity {self.cap}")
+        plan = ops.attn_seq_plan(lengths, spec.H).upload(m.device)
+        e = torch.empty((M, spec.D), dtype=m.dtype, device=m.device)
+        ops.embed_sum_fwd(tokens.contiguous(), m._W["net"].embed, e)
+        y = engine.stack_prefill_seqs(spec, m._W["net"], e, plan, self.rope1, self.kv1, folded=self.fold1)
+        self.hidden.copy_(y.index_select(0, plan.seq_start[1:].long() - 1))
+        self.pos.copy_(plan.seq_start[1:] - plan.seq_start[:-1])
 
     def begin(self, generator) -> None:
         """take over the caller's random stream (None = the device's default generator)"""
@@ -326,7 +373,8 @@ class DecodeSession:
             self.g_net.replay()
         else:
             self._net_body()
-        self.kv1.len += 1
+        if not self.ragged:  # (ragged: the rows' positions live in `pos` alone)
+            self.kv1.len += 1
 
     def tok_step(self, i: int) -> None:
         """sample token position i of the current event into seq[:, i] (and ev for i == 0) -- the step-by-step form.
@@ -405,8 +453,14 @@ class DecodeSession:
             return 2, True
         return (alive[0] + 1 if all(a == alive[0] for a in alive) else self.T), False
 
-    def sample_event(self, then_net: bool = False):
+    @staticmethod
+    def _live_ids(ids, live):
+        return ids if live is None else [t for t, on in zip(ids, live) if on]
+
+    def sample_event(self, then_net: bool = False, live=None):
         """sample the T tokens of the next event from `hidden`; -> (np.ndarray [B, T] int64, all rows ended?).
+        ``live`` (ragged; a bool per row): the break rule and "all rows ended" are evaluated over these rows only -- the others
+        are retired, sampled all the same, and the caller drops their tokens.
         ``then_net`` (graph form): the net step over the sampled event is queued right behind the token steps, BEFORE the host
         waits for the tokens -- it depends on nothing the host decides -- so the device never idles through the host's
         round trip; the tokens come back through a copy stream that waits for the token steps only.  (If every row turns out
@@ -432,13 +486,13 @@ class DecodeSession:
                     event = self.seq_host.numpy().copy()
             else:
                 event = self.seq.cpu().numpy().copy()  # the one host sync per event
-            n, end_all = self.n_steps_of(event[:, 0].tolist())
+            n, end_all = self.n_steps_of(self._live_ids(event[:, 0].tolist(), live))
             self.consumed(n)
             return event, end_all
         n_steps, end_all, i = self.T, False, 0
         while i < n_steps:
             self.tok_step(i)  # ... lm_head -> masked softmax -> sample_top_p_k -> seq[:, i]
             if i == 0:
-                n_steps, end_all = self.n_steps_of(self.ev.tolist())  # (a host sync)
+                n_steps, end_all = self.n_steps_of(self._live_ids(self.ev.tolist(), live))  # (a host sync)
             i += 1
         return self.seq.cpu().numpy().copy(), end_all  # (a CPU tensor would share memory with the session buffer)

@@ -514,12 +514,13 @@ def stack_forward(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, 
     ``first`` (token-level stack, training): what the rows ``x`` were laid out from; where the folded training blocks run and
     tokfirst.table_first_ok holds, the first block takes tok_first_forward and stack_backward returns TokFirstGrads.
     ``seqs`` (event-level stack, training / validation): an uploaded ops.SeqPlan -- the rows are a PACKED batch, sequences of any
-    lengths laid end to end (data.PackedBatch); ``nseq`` / ``slen`` are then 1 / M and only the attention and RoPE see the table."""
+    lengths laid end to end (data.PackedBatch); ``nseq`` / ``slen`` are then 1 / M and only the attention and RoPE see the table.
+    With ``kv_out`` it is a ragged prefill (stack_prefill_seqs): the qkv handed out are rotated at the rows' own positions."""
     _check_heads(spec)
     M, D = x.shape
     assert M == nseq * slen
     if seqs is not None:
-        assert spec.kind == "event" and kv_out is None and first is None and seqs.M == M and seqs.H == spec.H
+        assert spec.kind == "event" and first is None and seqs.M == M and seqs.H == spec.H
         rope.ensure(seqs.max_len)
     else:
         rope.ensure(slen)
@@ -611,6 +612,20 @@ def stack_prefill(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, 
     return y
 
 
+def stack_prefill_seqs(spec: StackSpec, W: StackTensors, x: torch.Tensor, plan, rope: RopeTable, kv: KVState, folded=None):
+    """stack_prefill for prompts of DIFFERENT lengths (generate_ragged): ``x`` [M, D] holds plan.n sequences laid end to end
+    (``plan`` = an uploaded ops.SeqPlan), sequence s fills rows [0, L_s) of its own cache -- one packed forward, then one
+    kv_store_seqs launch per layer.  kv.len is left alone: the rows stand at different positions, which the caller keeps
+    (a ragged decode session: ``pos`` on the device)."""
+    assert kv.B == plan.n and plan.M == x.shape[0]
+    kv.reserve(plan.max_len)
+    qkvs: list = []
+    y, _ = stack_forward(spec, W, x, 1, plan.M, rope, save=False, kv_out=qkvs, folded=folded, seqs=plan)
+    for li, qkv in enumerate(qkvs):
+        ops.kv_store_seqs(qkv, plan, kv.k[li], kv.v[li], spec.H, spec.hd, kv.cap)
+    return y
+
+
 def stack_extend(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable, kv: KVState):
     """A chunk of ``slen`` > 1 new positions per sequence behind ``kv.len`` cached ones (a cache-carrying forward with q_len > 1:
     chunked prefill, TF:models/llama/modeling_llama.py:386-389 position offset + TF:integrations/sdpa_attention.py:79-166).
@@ -676,7 +691,8 @@ class _FoldList(list):
 
 
 def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTable, kv: KVState, pos_dev=None,
-                 folded=None, final_norm: bool = True, x_ids=None, out: Optional[torch.Tensor] = None, shared=None):
+                 folded=None, final_norm: bool = True, x_ids=None, out: Optional[torch.Tensor] = None, shared=None,
+                 row_pos=None):
     """x [B, D]: one new position per sequence at index kv.len (q_len == 1 => no causal mask,
     TF:integrations/sdpa_attention.py:120).
 
@@ -692,13 +708,25 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
     whose K/V sit once in ``kvp`` (a KVState of one sequence, kvp.len rows) and ``kv`` holds only each row's suffix.  The
     position is kvp.len + kv.len (RoPE runs there), the new K/V row goes to suffix row kv.len, and in every form of the layer the
     attention step is the two launches of shared.py (attn_prefix_partial, attn_decode_append_shared: +1 launch per layer against
-    the fused forms).  pre_len_dev goes with pos_dev: device int32[1] values a captured graph reads."""
+    the fused forms).  pre_len_dev goes with pos_dev: device int32[1] values a captured graph reads.
+    ``row_pos`` (device int32 [B]; event level, head_dim 64; generate_ragged): row b stands at position row_pos[b] of its own
+    cache -- RoPE there, K/V stored at that row, attention over rows [0, row_pos[b]] -- and the attention step of every form of the
+    layer is the per-row entry point (same launch count).  The positions are always read on the device, eagerly too, so capacity,
+    rope table and kv.len are the caller's business, as with pos_dev.  Not together with ``shared`` or ``pos_dev``."""
     _check_heads(spec)
     B, D = (x_ids.shape[0], x.shape[1]) if x_ids is not None else x.shape
     assert x_ids is None or folded is not None
     H, I, hd = spec.H, spec.I, spec.hd
+    assert row_pos is None or (shared is None and pos_dev is None and spec.kind == "event")
     pos = kv.len if pos_dev is None else 0
-    attend_shared = None
+    attend = None  # what takes the place of the attention step, in all three forms of the layer
+    if row_pos is not None:
+        def attend(qkv, o, li):
+            if fused:
+                ops.attn_decode_append_rows(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, spec.scale, row_pos)
+            else:
+                ops.kv_append_rows(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], B, H, hd, kv.cap, row_pos)
+                ops.attn_decode_rows(qkv, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, spec.scale, row_pos)
     if shared is not None:
         from . import shared as sp
         kvp, pre_len_dev, ws = shared
@@ -706,12 +734,12 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
         pre, row = (kvp.len, kv.len) if pos_dev is None else (0, 0)
         pos = pre + row
 
-        def attend_shared(qkv, o, li):
+        def attend(qkv, o, li):
             sp.attn_prefix_partial(qkv, rope.cos, rope.sin, kvp.k[li], kvp.v[li], ws, B, H, hd, kvp.cap, pre, pos, spec.scale,
                                    pre_len_dev, pos_dev)
             sp.attn_decode_append_shared(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], ws, o, B, H, hd, kv.cap, kvp.cap, pre, pos,
                                          spec.scale, pre_len_dev, pos_dev)
-    if pos_dev is None:
+    if pos_dev is None and row_pos is None:
         kv.reserve((pos if shared is None else kv.len) + 1)
         rope.ensure(pos + 1)
     fused = (x_ids is not None) or (ops.skinny_ok(x, D) and ops.skinny_ok(x, I))
@@ -722,8 +750,8 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
             qkv = _empty((B, 3 * D), x)
             ops.gemm_skinny(x, wqkv_n, qkv, norm_eps=spec.eps, row_ids=ids)
             o = _empty((B, D), x)
-            if attend_shared is not None:
-                attend_shared(qkv, o, li)
+            if attend is not None:
+                attend(qkv, o, li)
             else:
                 ops.attn_decode_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos, spec.scale, pos_dev)
             x2 = _empty((B, D), x)
@@ -740,8 +768,8 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
             qkv = _empty((B, 3 * D), x)
             ops.gemm_skinny(h1, lw.wqkv, qkv)
             o = h1
-            if attend_shared is not None:
-                attend_shared(qkv, o, li)
+            if attend is not None:
+                attend(qkv, o, li)
             else:
                 ops.attn_decode_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos, spec.scale, pos_dev)
             x2 = _empty((B, D), x)
@@ -759,8 +787,8 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
         qkv = _empty((B, 3 * D), x)
         ops.gemm_nt(h1, lw.wqkv, qkv)
         o = h1
-        if attend_shared is not None:
-            attend_shared(qkv, o, li)
+        if attend is not None:
+            attend(qkv, o, li)
         else:
             ops.kv_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], B, H, hd, kv.cap, pos, pos_dev)
             ops.attn_decode(qkv, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos + 1, spec.scale, pos_dev)
@@ -775,7 +803,7 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
         x3 = _empty((B, D), x)
         ops.gemm_nt(a, lw.wd, x3, beta=1.0, res=x2)
         x = x3
-    if pos_dev is None:
+    if pos_dev is None and row_pos is None:
         kv.len = (pos if shared is None else kv.len) + 1
     if not final_norm:
         return x

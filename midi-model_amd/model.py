@@ -494,6 +494,104 @@ class MIDIModel(nn.Module):
         return self._generate_events(inp, batch_size, max_len, temp, top_p, top_k, generator, False,
                                      disable_patch_change, disable_control_change, disable_channels, shared)
 
+    def generate_ragged(self, prompts, max_len=512, temp=1.0, top_p=0.98, top_k=20, disable_patch_change=False,
+                        disable_control_change=False, disable_channels=None, generator=None, ban_eos: bool = False):
+        """(ours) ``generate`` for B prompts of B DIFFERENT lengths in ONE decode batch: ``prompts`` is a sequence of B arrays, row
+        b of shape ``(L_b, T')``, 1 <= T' <= 8, padded and range-checked as ``generate`` pads and checks its prompt.  Returns a
+        list of B ``np.ndarray (<= max_len, 8) int64``, row b with its prompt in front.
+
+        The rows decode in lockstep: event step t samples one event for every row, and row b is live while L_b + t < max_len.
+        A row that reaches ``max_len`` is retired: the device parks it at position max_len and goes on sampling it (no host
+        bookkeeping per row, no extra sync; decode.py), the host drops what it samples.  The reference's break rule and its
+        "every row sampled EOS" stop are evaluated over the live rows only, so with equal lengths this is the rule ``generate``
+        runs; the noise is still ``[8, B, V]`` per event.  The call ends when no row is live or every live row sampled EOS, so a
+        row may come back shorter than ``max_len`` only through EOS.  The set of rows is fixed for the call; temperature, top-p,
+        top-k and ``max_len`` are the call's, not a row's.  ``ValueError`` before any launch: no prompts, an empty prompt, a
+        prompt of ``max_len`` events or more, ids outside the vocabulary, and what the mask options refuse in ``generate``.
+        The prompts are prefilled packed -- no padded event is computed.
+        Speed against one ``generate`` call per distinct length: NOT MEASURED at this commit -- ``tools/bench_ragged.py`` is the
+        vehicle and no MI355X run of it exists yet.  From launches alone: a decoded event costs about the same
+        ~210 launches for 1 row as for 64, so B lengths in one batch should approach B times the useful events/s of B batches
+        of one; the net graph gains two tiny launches (the position update) and nothing else."""
+        rows = self._ragged_prompts(prompts, max_len, None)
+        chans = self._check_mask_options(ban_eos, disable_patch_change, disable_control_change, disable_channels)
+        outs = [[r] for r in rows]
+        for ev, live in self._generate_events_ragged(rows, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
+                                                     disable_control_change, chans):
+            for b in np.flatnonzero(live):
+                outs[b].append(ev[b][None])
+        return [np.concatenate(o, axis=0) for o in outs]
+
+    def generate_stream_ragged(self, prompts, max_len=512, temp=1.0, top_p=0.98, top_k=20, disable_patch_change=False,
+                               disable_control_change=False, disable_channels=None, generator=None, ban_eos: bool = False):
+        """The serving form of ``generate_ragged``: a Python generator that yields, per event step, ``(events np.int64 (B, 8),
+        live np.bool_ (B,))`` -- row b of ``events`` counts only where ``live[b]``.  Each prompt is cropped to its last 4096
+        events first, as ``generate_stream`` crops.  The arguments are checked HERE, before the generator is handed out."""
+        rows = self._ragged_prompts(prompts, max_len, 4096)
+        chans = self._check_mask_options(ban_eos, disable_patch_change, disable_control_change, disable_channels)
+        return self._generate_events_ragged(rows, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
+                                            disable_control_change, chans)
+
+    def _ragged_prompts(self, prompts, max_len: int, crop) -> list:
+        """the prompts of generate_ragged as contiguous int64 arrays (L_b, 8): _prompt_tensor's range check and padding per row"""
+        self._require_gpu()
+        tok = self.tokenizer
+        T = tok.max_token_seq
+        if prompts is None or len(prompts) == 0:
+            raise ValueError("generate_ragged: no prompts")
+        rows = []
+        for b, p in enumerate(prompts):
+            p = np.asarray(p)
+            if p.ndim != 2 or p.shape[0] < 1 or p.shape[1] < 1:
+                raise ValueError(f"generate_ragged: prompt {b} has shape {p.shape}; (L, T') with L >= 1 and 1 <= T' <= {T} is needed")
+            if p.min() < 0 or p.max() >= tok.vocab_size:
+                raise ValueError(f"prompt holds token ids outside [0, {tok.vocab_size}): min {p.min()}, max {p.max()}")
+            p = p[:, :T]
+            if p.shape[1] < T:
+                p = np.pad(p, ((0, 0), (0, T - p.shape[1])), mode="constant", constant_values=tok.pad_id)
+            if crop is not None:
+                p = p[-crop:]
+            if p.shape[0] >= max_len:
+                raise ValueError(f"generate_ragged: prompt {b} has {p.shape[0]} events, max_len is {max_len}: nothing to generate")
+            rows.append(np.ascontiguousarray(p, dtype=np.int64))
+        return rows
+
+    def _generate_events_ragged(self, rows, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
+                                disable_control_change, chans):
+        """generator over (events (B, 8), live (B,)) of the checked prompts ``rows``; the session goes back to the pool when the
+        generator finishes or is closed.  The loop is _generate_events' with the live rows in place of all rows."""
+        lengths = np.array([r.shape[0] for r in rows], dtype=np.int64)
+        B = len(rows)
+        with torch.inference_mode():
+            ses = self._checkout_session(B, max_len + 1, float(temp), float(top_p), int(top_k), ragged=True)
+        try:
+            with torch.inference_mode():
+                self._set_masks(ses, ban_eos, disable_patch_change, disable_control_change, chans)
+                ses.reset()
+                ses.begin(generator)
+                ses.set_limit(max_len)
+                packed = torch.from_numpy(np.concatenate(rows, axis=0)).to(self.device)
+                ses.prefill_ragged(packed, lengths.tolist())  # one packed causal forward; hidden[b] = prompt b's last position
+            t = 0
+            while True:
+                live = lengths + t < max_len          # (row b's next event has index L_b + t)
+                with torch.inference_mode():
+                    more = bool((lengths + t + 1 < max_len).any())
+                    speculative = more and ses.g_steps is not None and _SPECULATIVE_NET
+                    event, end_all = ses.sample_event(then_net=speculative, live=live.tolist())
+                    t += 1
+                    last = end_all or not more
+                    if not last:
+                        ses.draw_noise()
+                        if not speculative:
+                            ses.net_step()
+                yield event, live
+                if last:
+                    break
+        finally:
+            ses.end()
+            self._return_session(ses)
+
     @staticmethod
     def _shares_prompt(prompt, share_prompt: bool) -> bool:
         """share_prompt=True with a prompt: its rows must be equal (host check, before any launch); without one: plain path"""
@@ -527,16 +625,9 @@ class MIDIModel(nn.Module):
                             constant_values=tok.pad_id)
         return torch.from_numpy(np.ascontiguousarray(prompt)).to(dtype=torch.long, device=dev)
 
-    def _generate_events(self, inp, batch_size, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
-                         disable_control_change, disable_channels, shared: bool = False):
-        """generator over the new events ((B, 8) int64 numpy each); the session is returned to the pool when the
-        generator finishes or is closed"""
+    def _check_mask_options(self, ban_eos, disable_patch_change, disable_control_change, disable_channels) -> list:
+        """the mask options of generate / generate_ragged, checked on the host before any launch; -> the banned channels, sorted"""
         tok = self.tokenizer
-        T = tok.max_token_seq
-        B = batch_size
-        cur_len = inp.shape[1]
-        if cur_len >= max_len:
-            return
         # Every grammar mask must keep at least one id.  The reference fails with a (recoverable) multinomial error when a
         # mask is empty (midi_model.py:152-165 on an all-zero row); the fused sampler has no such path -- it would hand a
         # sentinel id to the next embedding lookup, which traps -- so an emptied mask is refused here, before any launch.
@@ -555,6 +646,33 @@ class MIDIModel(nn.Module):
             raise ValueError(f"generate: disable_channels holds a channel outside [0, {n_chan}): {chans}")
         if len(chans) >= n_chan:
             raise ValueError("generate: disable_channels bans every channel id: no legal token is left at the channel position")
+        return chans
+
+    def _set_masks(self, ses, ban_eos, disable_patch_change, disable_control_change, chans) -> None:
+        """write the checked mask options into a session's first-token mask and ban list"""
+        tok = self.tokenizer
+        ses.first_mask.copy_(self._grammar()[0])
+        if ban_eos:
+            ses.first_mask[tok.eos_id] = 0
+        if disable_patch_change:
+            ses.first_mask[tok.event_ids["patch_change"]] = 0
+        if disable_control_change:
+            ses.first_mask[tok.event_ids["control_change"]] = 0
+        ses.ban.zero_()
+        for c in chans:
+            ses.ban[tok.parameter_ids["channel"][c]] = 1
+
+    def _generate_events(self, inp, batch_size, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
+                         disable_control_change, disable_channels, shared: bool = False):
+        """generator over the new events ((B, 8) int64 numpy each); the session is returned to the pool when the
+        generator finishes or is closed"""
+        tok = self.tokenizer
+        T = tok.max_token_seq
+        B = batch_size
+        cur_len = inp.shape[1]
+        if cur_len >= max_len:
+            return
+        chans = self._check_mask_options(ban_eos, disable_patch_change, disable_control_change, disable_channels)
         with torch.inference_mode():
             if shared:  # the prompt in its own cache; the per-row cache holds the generated suffix only
                 ses = self._checkout_session(B, max_len - cur_len + 1, float(temp), float(top_p), int(top_k), shared_need=cur_len)
@@ -562,16 +680,7 @@ class MIDIModel(nn.Module):
                 ses = self._checkout_session(B, max(max_len, cur_len) + 1, float(temp), float(top_p), int(top_k))
         try:
             with torch.inference_mode():
-                ses.first_mask.copy_(self._grammar()[0])
-                if ban_eos:
-                    ses.first_mask[tok.eos_id] = 0
-                if disable_patch_change:
-                    ses.first_mask[tok.event_ids["patch_change"]] = 0
-                if disable_control_change:
-                    ses.first_mask[tok.event_ids["control_change"]] = 0
-                ses.ban.zero_()
-                for c in chans:
-                    ses.ban[tok.parameter_ids["channel"][c]] = 1
+                self._set_masks(ses, ban_eos, disable_patch_change, disable_control_change, chans)
                 ses.reset()
                 ses.begin(generator)
                 ses.prefill(inp)  # causal forward over the prompt; hidden = last position
@@ -596,9 +705,11 @@ class MIDIModel(nn.Module):
             self._return_session(ses)
 
     # decode sessions: buffers + captured graphs, one per concurrent generate() call (decode.py)
-    def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int, shared_need: int = 0):
+    def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int, shared_need: int = 0,
+                          ragged: bool = False):
         """``shared_need`` > 0: a shared-prompt session whose prompt cache holds shared_need events (capacities by the same
-        doubling rule from 256, so one captured session serves a range of prompt and suffix lengths)"""
+        doubling rule from 256, so one captured session serves a range of prompt and suffix lengths).  ``ragged``: a session
+        with a position per row (generate_ragged), pooled like the others; not together with shared_need."""
         from .decode import DecodeSession
         cap = 256
         while cap < need:
@@ -608,7 +719,7 @@ class MIDIModel(nn.Module):
             scap = 256
             while scap < shared_need:
                 scap *= 2
-        key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap)
+        key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged)
         pool = self._sessions
         with pool.lock:
             found = None
@@ -621,7 +732,7 @@ class MIDIModel(nn.Module):
         if found is not None:
             found.refresh()  # weights may have been trained / merged since the session derived its folded copies
             return found
-        return DecodeSession(self, B, cap, temp, top_p, top_k, scap)
+        return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged)
 
     def _return_session(self, ses) -> None:
         with self._sessions.lock:

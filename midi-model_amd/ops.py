@@ -593,7 +593,9 @@ def attn_bwd(qkv, o, dout, lse, dqkv, B: int, S: int, H: int, scale: float, cos_
 # own for every public callable it finds in dir(ops), and that file predates these entry points; their stand-ins are in
 # tests/emu_packed.py, installed on top of it.  Moving the five functions here needs stand-ins in emu_ops.py in the same change --
 # without them every host test that installs the emulation fails at its completeness check.
-_PACKED = ("SeqPlan", "attn_seq_plan", "rope_pos_", "attn_fwd_seqs", "attn_bwd_seqs")
+# The per-row decode forms and the packed K/V store (generate_ragged) are resolved the same way, for the same reason.
+_PACKED = ("SeqPlan", "attn_seq_plan", "rope_pos_", "attn_fwd_seqs", "attn_bwd_seqs",
+           "kv_append_rows", "attn_decode_rows", "attn_decode_append_rows", "kv_store_seqs")
 
 
 def __getattr__(name: str):

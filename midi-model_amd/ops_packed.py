@@ -168,3 +168,39 @@ def attn_bwd_seqs(qkv, o, dout, lse, dqkv, plan: SeqPlan, H: int, scale: float, 
     lib().call("mh_attn_bwd_seqs", _p(qkv), _p(o), _p(dout), _p(lse), _p(scratch), _p(dqkv), _p(rowscale), _p(plan.seq_start),
                _p(plan.work), plan.nwork, plan.M, plan.Mpad, plan.max_len, H, scale, _p(cos_t), _p(sin_t), dt(qkv), _stream())
     return dqkv
+
+
+# -------------------------------------------------------------------------- ragged decode (MIDIModel.generate_ragged)
+def _row_pos_check(row_pos, B: int, qkv: torch.Tensor):
+    assert row_pos is not None and row_pos.dtype == torch.int32 and row_pos.shape == (B,) and row_pos.is_contiguous()
+    assert row_pos.device == qkv.device
+
+
+def kv_append_rows(qkv, cos_t, sin_t, kc, vc, B: int, H: int, hd: int, Lmax: int, row_pos):
+    """kv_append with sequence b at position row_pos[b] (int32 [B] on the device)"""
+    _row_pos_check(row_pos, B, qkv)
+    lib().call("mh_kv_append_rows", _p(qkv), _p(cos_t), _p(sin_t), _p(kc), _p(vc), B, H, hd, Lmax, _p(row_pos), dt(qkv), _stream())
+
+
+def attn_decode_rows(qkv, kc, vc, o, B: int, H: int, hd: int, Lmax: int, scale: float, row_pos):
+    """attn_decode with sequence b attending to its cache rows [0, row_pos[b]]"""
+    _row_pos_check(row_pos, B, qkv)
+    lib().call("mh_attn_decode_rows", _p(qkv), _p(kc), _p(vc), _p(o), B, H, hd, Lmax, scale, _p(row_pos), dt(qkv), _stream())
+    return o
+
+
+def attn_decode_append_rows(qkv, cos_t, sin_t, kc, vc, o, B: int, H: int, hd: int, Lmax: int, scale: float, row_pos):
+    """kv_append_rows + attn_decode_rows in one launch (qkv is read unrotated and left untouched)"""
+    _row_pos_check(row_pos, B, qkv)
+    lib().call("mh_attn_decode_append_rows", _p(qkv), _p(cos_t), _p(sin_t), _p(kc), _p(vc), _p(o), B, H, hd, Lmax, scale,
+               _p(row_pos), dt(qkv), _stream())
+    return o
+
+
+def kv_store_seqs(qkv, plan: SeqPlan, kc, vc, H: int, hd: int, Lmax: int):
+    """the rotated K, V of a packed prefill -> cache rows [0, L_s) of every sequence s of ``plan``; kc / vc [n, H, Lmax, hd]"""
+    assert plan.dev is not None, "SeqPlan.upload(device) first"
+    assert qkv.shape == (plan.M, 3 * H * hd) and qkv.is_contiguous() and kc.shape[0] == plan.n
+    if plan.max_len > Lmax:
+        raise ValueError(f"kv_store_seqs: a sequence of {plan.max_len} rows in a cache of {Lmax}")
+    lib().call("mh_kv_store_seqs", _p(qkv), _p(plan.seq_start), _p(kc), _p(vc), plan.n, plan.M, H, hd, Lmax, dt(qkv), _stream())
