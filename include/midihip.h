@@ -157,6 +157,13 @@ int mh_gemm_splitk_reduce(const void* workspace, void* C, int64_t ldc, const voi
 int mh_gemm_skinny(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* R,
                    int64_t ldr, int mode, float norm_eps, const int64_t* row_ids, const int64_t* res_ids, int64_t M,
                    int64_t N, int64_t K, int dtype, void* stream);
+/* mh_gemm_skinny for a decode batch of 65 to 256 rows: the same arguments, epilogues, row scaling, gathers and roundings, for
+ * 64 < M <= 256 (anything else is refused: 1..64 rows belong to mh_gemm_skinny, more than 256 to mh_gemm).  Rows are taken in
+ * groups of 64 by the second grid dimension; all of K stays in the workgroup.  LIMITS as above with 256 in place of 64:
+ * 256 * lda, 256 * ldc, 256 * ldr < 2^31. */
+int mh_gemm_skinny_wide(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* R,
+                        int64_t ldr, int mode, float norm_eps, const int64_t* row_ids, const int64_t* res_ids, int64_t M,
+                        int64_t N, int64_t K, int dtype, void* stream);
 /* out[C,R] = in[R,C]^T (operand re-layout for dgrad/wgrad). */
 int mh_transpose(const void* in, int64_t ldi, void* out, int64_t ldo, int64_t rows, int64_t cols, int dtype,
                  void* stream);

@@ -292,6 +292,45 @@ extern "C" int mh_gemm_skinny(const void* A, int64_t lda, const void* W, int64_t
   else if (nbt == 2 && N > 4096) MH_SK(0, 2, 4, (N + 31) / 32);
   else if (nbt == 2) MH_SK(0, 2, 8, (N + 31) / 32);
   else MH_SK(0, 1, 8, (N + 15) / 16);  // 16 columns x 8 waves: <= 4 chunks per wave at K = 1024, all in flight
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// The same projection for 64 < M <= 256 rows (a decode batch of 65 to 256 sequences): the kernel above on a grid of
+// ceil(M / 64) row groups.  The kernel never assumed one row group -- blockIdx.y * MR is its first row, rows past M are clamped
+// for the loads and not written -- so the wide entry point is a launcher of its own over the SAME instantiations (the narrow
+// entry point's code objects are untouched): all of K stays in the workgroup, every row group takes the 64-row form
+// (MB = 4: the activation rows a workgroup re-reads per weight byte are at their fewest), and the column tile follows the
+// narrow rule.  The workgroups of one column tile have ids b, b + gridDim.x, ...: their weight slab comes from HBM once and
+// from L2 for the other row groups.  The 32-bit offset guards are those of the narrow entry point for 256 rows.
+extern "C" int mh_gemm_skinny_wide(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* R,
+                                   int64_t ldr, int mode, float norm_eps, const int64_t* row_ids, const int64_t* res_ids,
+                                   int64_t M, int64_t N, int64_t K, int dtype, void* stream) {
+  MH_REQUIRE(dtype == MH_BF16, "gemm_skinny_wide: bf16 only (the fp32 verification mode uses mh_gemm)");
+  MH_REQUIRE(M > 64 && M <= 256 && N > 0 && N < (1 << 24),
+             "gemm_skinny_wide: needs 65 <= M <= 256 rows, mh_gemm_skinny serves 1..64 (M=%ld N=%ld)", (long)M, (long)N);
+  MH_REQUIRE(mode == MH_SKINNY_PLAIN || mode == MH_SKINNY_GATEUP, "gemm_skinny_wide: mode %d", mode);
+  MH_REQUIRE(K > 0 && K % 256 == 0 && K < (1 << 24), "gemm_skinny_wide: K=%ld must be a multiple of 256", (long)K);
+  MH_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0,
+             "gemm_skinny_wide: A/W rows must be 16-byte aligned");
+  MH_REQUIRE(mode != MH_SKINNY_GATEUP || R == nullptr, "gemm_skinny_wide: the gate|up epilogue takes no residual");
+  MH_REQUIRE((mode == MH_SKINNY_GATEUP ? 2 * N : N) * ldw < (int64_t(1) << 31) && 256 * lda < (int64_t(1) << 31) &&
+                 256 * ldc < (int64_t(1) << 31) && (R == nullptr || 256 * ldr < (int64_t(1) << 31)) && lda < (int64_t(1) << 24) &&
+                 ldr < (int64_t(1) << 24),
+             "gemm_skinny_wide: operands too large for 32-bit element offsets");
+  hipStream_t st = (hipStream_t)stream;
+  const int mb = 4;                         // 64 rows per workgroup, the last group ragged
+  const int gy = (int)((M + 63) / 64);      // 2..4 row groups
+  const int nbt = (mode == MH_SKINNY_GATEUP) ? 2 : (N >= 2048 ? 2 : 1);
+  const int group_bytes = ((mode == MH_SKINNY_GATEUP || nbt == 1) ? 4 : 8) * 2;
+  const int vec = (((uintptr_t)C % group_bytes) == 0 && (ldc * 2) % group_bytes == 0) ? 1 : 0;
+  // (one class is kept off the batch rule above: two column blocks on 8 waves with the row scale and 8 or 16 chunks per wave would
+  //  take the batch of 8, the one 64-row instantiation the compiler gives scratch (8 bytes per lane); batches of 4 hold no scratch)
+  if (mode == MH_SKINNY_PLAIN && nbt == 2 && N <= 4096 && norm_eps > 0.f && (K / 256) % 8 == 0) MH_SK4(0, 2, 8, (N + 31) / 32, true, 4, 4);
+  else if (mode == MH_SKINNY_GATEUP) MH_SK(1, 2, 4, (N + 15) / 16);
+  else if (nbt == 2 && N > 4096) MH_SK(0, 2, 4, (N + 31) / 32);
+  else if (nbt == 2) MH_SK(0, 2, 8, (N + 31) / 32);
+  else MH_SK(0, 1, 8, (N + 15) / 16);
 #undef MH_SK
 #undef MH_SK2
 #undef MH_SK3

@@ -111,7 +111,10 @@ class DecodeSession:
         # RMSNorm weights folded into the projections that follow them (one launch for norm + projection)
         self.fold1 = self.fold2 = self.lm_fold = None
         probe = torch.empty((B, 1), dtype=dt, device=dev)
-        if ops.skinny_ok(probe, spec.D) and ops.skinny_ok(probe, spec.I) and ops.skinny_ok(probe, tspec.I) \
+        # 65 to 256 rows: the same folded layer on mh_gemm_skinny_wide, unless MH_DECODE_WIDE=0 (read here, once) keeps the general form
+        self.wide = ops.decode_wide_enabled() and ops.skinny_wide_ok(probe, spec.D)
+        served = ops.skinny_wide_ok if self.wide else ops.skinny_ok
+        if served(probe, spec.D) and served(probe, spec.I) and served(probe, tspec.I) \
                 and os.environ.get("MH_DECODE_FOLD", "1") != "0":
             self.fold1 = engine.fold_norm_weights(model._W["net"])
             self.fold2 = engine.fold_norm_weights(model._W["net_token"])
@@ -162,7 +165,8 @@ class DecodeSession:
         e = torch.empty((self.B, spec.D), dtype=m.dtype, device=m.device)
         ops.embed_sum_fwd(self.seq, m._W["net"].embed, e)  # the event sampled last
         if self.ragged:  # every row at its own position; a row at pos_limit stays there
-            engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, folded=self.fold1, out=self.hidden, row_pos=self.pos)
+            engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, folded=self.fold1, out=self.hidden, row_pos=self.pos,
+                                wide=self.wide)
             self.pos.add_(1)
             torch.minimum(self.pos, self.pos_limit, out=self.pos)
             return
@@ -171,7 +175,7 @@ class DecodeSession:
             from .shared import SharedPrefix
             sh = SharedPrefix(self.kvp, self.pre_len, self.ws)
         engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, pos_dev=self.pos, folded=self.fold1, out=self.hidden,
-                            shared=sh)
+                            shared=sh, wide=self.wide)
         self.pos.add_(1)
 
     def _noise_body(self, generator=None):
@@ -184,18 +188,20 @@ class DecodeSession:
         tspec, Wt = m._specs["net_token"], m._W["net_token"]
         self.kv2.len = i
         lm_w = m.lm_head.weight.data
+        skinny = ops.gemm_skinny_wide if self.wide else ops.gemm_skinny
         if self.lm_fold is not None:  # the stack's final RMSNorm rides on the lm_head projection
             if i == 0:
-                h = engine.stack_decode(tspec, Wt, self.hidden, self.rope2, self.kv2, folded=self.fold2, final_norm=False)
+                h = engine.stack_decode(tspec, Wt, self.hidden, self.rope2, self.kv2, folded=self.fold2, final_norm=False,
+                                        wide=self.wide)
             else:  # the embedding of the token just sampled is looked up inside the first projections
                 h = engine.stack_decode(tspec, Wt, Wt.embed, self.rope2, self.kv2, folded=self.fold2, final_norm=False,
-                                        x_ids=self.samples_in)
-            ops.gemm_skinny(h, self.lm_fold, self.logits[:, : self.V], norm_eps=tspec.eps)
+                                        x_ids=self.samples_in, wide=self.wide)
+            skinny(h, self.lm_fold, self.logits[:, : self.V], norm_eps=tspec.eps)
         else:
             x = self.hidden if i == 0 else Wt.embed.index_select(0, self.samples_in)
-            h = engine.stack_decode(tspec, Wt, x, self.rope2, self.kv2)
-            if ops.skinny_ok(h, tspec.D):
-                ops.gemm_skinny(h, lm_w, self.logits[:, : self.V])
+            h = engine.stack_decode(tspec, Wt, x, self.rope2, self.kv2, wide=self.wide)
+            if (ops.skinny_wide_ok if self.wide else ops.skinny_ok)(h, tspec.D):
+                skinny(h, lm_w, self.logits[:, : self.V])
             else:
                 ops.gemm_nt(h, lm_w, self.logits[:, : self.V])
         if i == 0 and not self.fused_sampler:
@@ -325,7 +331,8 @@ class DecodeSession:
 
     def prefill_ragged(self, tokens: torch.Tensor, lengths) -> None:
         """tokens [M, T]: the B prompts laid end to end, prompt b of lengths[b] events.  One packed causal forward from empty
-        caches (engine.stack_prefill_seqs); leaves hidden[b] = prompt b's last position and pos[b] = lengths[b]."""
+        caches (engine.stack_prefill_seqs); leaves hidden[b] = prompt b's last position and pos[b] = lengths[b].  Prompts of one
+        length take prefill()'s uniform forward instead, so that generate_ragged continues them exactly as generate() does."""
         m = self.model
         spec = m._specs["net"]
         lengths = [int(n) for n in lengths]
@@ -335,6 +342,19 @@ class DecodeSession:
                              f"{self.B} rows (ragged: {self.ragged})")
         if max(lengths) >= self.cap:
             raise ValueError(f"prompt of {max(lengths)} events in a ragged session of capacity {self.cap}")
+        if min(lengths) == max(lengths):
+            # prompts of ONE length are a uniform batch: the forward prefill() runs (RoPE in the q|k|v epilogue, no table), so the
+            # state handed to the decode steps is prefill()'s bit for bit -- the packed forward rotates the ROUNDED product in a
+            # launch of its own and lands a bf16 rounding away (hidden by up to 7.8e-2 on tv2o-medium), enough to part sampled ids
+            S = lengths[0]
+            e = torch.empty((M, spec.D), dtype=m.dtype, device=m.device)
+            ops.embed_sum_fwd(tokens.contiguous(), m._W["net"].embed, e)
+            self.kv1.len = 0
+            y = engine.stack_prefill(spec, m._W["net"], e, self.B, S, self.rope1, self.kv1, folded=self.fold1)
+            self.kv1.len = 0  # (ragged: the rows' positions live in `pos` alone)
+            self.hidden.copy_(y.view(self.B, S, spec.D)[:, -1])
+            self.pos.fill_(S)
+            return
         plan = ops.attn_seq_plan(lengths, spec.H).upload(m.device)
         e = torch.empty((M, spec.D), dtype=m.dtype, device=m.device)
         ops.embed_sum_fwd(tokens.contiguous(), m._W["net"].embed, e)

@@ -692,15 +692,18 @@ class _FoldList(list):
 
 def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTable, kv: KVState, pos_dev=None,
                  folded=None, final_norm: bool = True, x_ids=None, out: Optional[torch.Tensor] = None, shared=None,
-                 row_pos=None):
+                 row_pos=None, wide: Optional[bool] = None):
     """x [B, D]: one new position per sequence at index kv.len (q_len == 1 => no causal mask,
     TF:integrations/sdpa_attention.py:120).
 
     With ``pos_dev`` (device int32[1]) the kernels take the position from device memory instead -- the form a captured
     hipGraph replays (decode.py); capacity and rope table must already cover it and kv.len is left to the caller.
-    bf16 with at most 64 sequences runs the projections on mh_gemm_skinny: 7 launches per layer (K/V append fused
+    bf16 with at most 256 sequences runs the projections on the skinny kernels -- mh_gemm_skinny up to 64 rows,
+    mh_gemm_skinny_wide from 65 to 256 (the same arithmetic on more row groups): 7 launches per layer (K/V append fused
     into the attention, gate|up and SwiGLU fused), 5 with ``folded`` (fold_norm_weights: the two RMSNorms ride on the
-    q|k|v and gate|up projections); otherwise the general GEMM is used (9 launches + split-K reductions).
+    q|k|v and gate|up projections); otherwise (fp32, more than 256 rows) the general GEMM is used (9 launches + split-K
+    reductions).  ``wide=False`` sends 65 to 256 rows to the general form as well (None: MH_DECODE_WIDE, read here; a decode
+    session reads it once and passes what it read).
     ``final_norm=False`` returns the residual stream before the stack's last RMSNorm (decode.py folds it into lm_head).
     ``x_ids`` (folded form only): ``x`` is an embedding table and row b of the input is x[x_ids[b]] -- the lookup happens
     inside the first layer's projections.
@@ -742,44 +745,51 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
     if pos_dev is None and row_pos is None:
         kv.reserve((pos if shared is None else kv.len) + 1)
         rope.ensure(pos + 1)
-    fused = (x_ids is not None) or (ops.skinny_ok(x, D) and ops.skinny_ok(x, I))
+    if wide is None:
+        wide = ops.decode_wide_enabled()
+    # (rows=B: with x_ids, x is the embedding table and the step has as many rows as there are ids)
+    use_wide = wide and ops.skinny_wide_ok(x, D, rows=B) and ops.skinny_wide_ok(x, I, rows=B)
+    # x_ids come from a session with folds, which exists only where one of the two skinny entry points serves B rows
+    assert x_ids is None or use_wide or B <= 64, "stack_decode: x_ids with a row count no skinny entry point serves"
+    fused = (x_ids is not None) or use_wide or (ops.skinny_ok(x, D) and ops.skinny_ok(x, I))
+    skinny = ops.gemm_skinny_wide if use_wide else ops.gemm_skinny  # one entry point per row-count class, same arguments
     for li, lw in enumerate(W.layers):
         if fused and folded is not None:
             wqkv_n, wgu_n = folded[li]
             ids = x_ids if li == 0 else None  # layer 0 may read its input rows straight from the embedding table
             qkv = _empty((B, 3 * D), x)
-            ops.gemm_skinny(x, wqkv_n, qkv, norm_eps=spec.eps, row_ids=ids)
+            skinny(x, wqkv_n, qkv, norm_eps=spec.eps, row_ids=ids)
             o = _empty((B, D), x)
             if attend is not None:
                 attend(qkv, o, li)
             else:
                 ops.attn_decode_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos, spec.scale, pos_dev)
             x2 = _empty((B, D), x)
-            ops.gemm_skinny(o, lw.wo, x2, res=x, res_ids=ids)
+            skinny(o, lw.wo, x2, res=x, res_ids=ids)
             a = _empty((B, I), x)
-            ops.gemm_skinny(x2, wgu_n, a, mode=ops.SKINNY_GATEUP, norm_eps=spec.eps)
+            skinny(x2, wgu_n, a, mode=ops.SKINNY_GATEUP, norm_eps=spec.eps)
             x3 = _empty((B, D), x)
-            ops.gemm_skinny(a, lw.wd, x3, res=x2)
+            skinny(a, lw.wd, x3, res=x2)
             x = x3
             continue
         if fused:
             h1 = _empty((B, D), x)
             ops.rmsnorm_fwd(x, lw.n1, h1, None, spec.eps)
             qkv = _empty((B, 3 * D), x)
-            ops.gemm_skinny(h1, lw.wqkv, qkv)
+            skinny(h1, lw.wqkv, qkv)
             o = h1
             if attend is not None:
                 attend(qkv, o, li)
             else:
                 ops.attn_decode_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos, spec.scale, pos_dev)
             x2 = _empty((B, D), x)
-            ops.gemm_skinny(o, lw.wo, x2, res=x)
+            skinny(o, lw.wo, x2, res=x)
             h2 = o
             ops.rmsnorm_fwd(x2, lw.n2, h2, None, spec.eps)
             a = _empty((B, I), x)
-            ops.gemm_skinny(h2, lw.wgu, a, mode=ops.SKINNY_GATEUP)  # gate|up never materialised
+            skinny(h2, lw.wgu, a, mode=ops.SKINNY_GATEUP)  # gate|up never materialised
             x3 = _empty((B, D), x)
-            ops.gemm_skinny(a, lw.wd, x3, res=x2)
+            skinny(a, lw.wd, x3, res=x2)
             x = x3
             continue
         h1 = _empty((B, D), x)

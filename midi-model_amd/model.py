@@ -462,6 +462,12 @@ class MIDIModel(nn.Module):
         from the first-token mask (throughput runs); ``disable_patch_change`` / ``disable_control_change`` /
         ``disable_channels`` are the mask options of the serving loop (app.py:27-31, 73-86).
 
+        ``batch_size``: bf16 batches of up to 256 rows run the folded 5-launch decoder layer, the three graphs per event and the
+        fused sampler -- up to 64 rows on ``mh_gemm_skinny``, 65 to 256 on ``mh_gemm_skinny_wide`` (the same kernel over 64-row
+        groups; DESIGN 7.5 has the measured rates).  Larger batches and fp32 keep the general GEMM form (about twice the launches),
+        and so does ``MH_DECODE_WIDE=0`` from 65 rows up (read when a session is created).  The same holds for ``generate_stream``,
+        ``generate_ragged`` and ``share_prompt``.
+
         ``share_prompt=True`` (ours; what every caller of the reference does: B continuations of ONE prompt) takes a
         ``(L, T')`` prompt, a ``(1, L, T')`` prompt or a ``(batch_size, L, T')`` prompt whose rows are all equal (checked on the
         host; unequal rows raise ``ValueError`` naming the first row that differs).  The prompt is prefilled once instead of B
@@ -508,7 +514,8 @@ class MIDIModel(nn.Module):
         row may come back shorter than ``max_len`` only through EOS.  The set of rows is fixed for the call; temperature, top-p,
         top-k and ``max_len`` are the call's, not a row's.  ``ValueError`` before any launch: no prompts, an empty prompt, a
         prompt of ``max_len`` events or more, ids outside the vocabulary, and what the mask options refuse in ``generate``.
-        The prompts are prefilled packed -- no padded event is computed.
+        The prompts are prefilled packed -- no padded event is computed; prompts of ONE length are prefilled by
+        ``generate``'s uniform forward, so that for the same seeded generator the call returns exactly ``generate``'s ids.
         Speed against one ``generate`` call per distinct length: NOT MEASURED at this commit -- ``tools/bench_ragged.py`` is the
         vehicle and no MI355X run of it exists yet.  From launches alone: a decoded event costs about the same
         ~210 launches for 1 row as for 64, so B lengths in one batch should approach B times the useful events/s of B batches

@@ -299,7 +299,7 @@ SKINNY_PLAIN, SKINNY_GATEUP = 0, 1
 def gemm_skinny(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, mode: int = SKINNY_PLAIN,
                 res: Optional[torch.Tensor] = None, norm_eps: float = 0.0, row_ids: Optional[torch.Tensor] = None,
                 res_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """decode-step projection, M <= 64 rows, bf16 (mh_gemm_skinny): out[M,N] = a @ w[N,K]^T (+ res), or with
+    """decode-step projection, M <= 64 rows, bf16 (mh_gemm_skinny; 65 to 256 rows: gemm_skinny_wide): out[M,N] = a @ w[N,K]^T (+ res), or with
     SKINNY_GATEUP w = [gate; up] ([2N,K]) and out[M,N] = silu(a @ gate^T) * (a @ up^T).  norm_eps > 0 scales row m of
     the product by rsqrt(mean(a[m]^2) + norm_eps) first (RMSNorm with its weight folded into w).  row_ids / res_ids
     (int64 [M]): `a` / `res` are tables and row m is their row ids[m] (embedding lookup folded in)."""
@@ -318,7 +318,7 @@ def gemm_skinny(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, mode: in
 
 
 def skinny_ok(x: torch.Tensor, K: int) -> bool:
-    """whether mh_gemm_skinny serves this decode projection (else mh_gemm)"""
+    """whether mh_gemm_skinny serves this decode projection (else skinny_wide_ok / mh_gemm_skinny_wide up to 256 rows, else mh_gemm)"""
     return x.dtype == torch.bfloat16 and x.shape[0] <= 64 and K % 256 == 0
 
 
@@ -596,12 +596,17 @@ def attn_bwd(qkv, o, dout, lse, dqkv, B: int, S: int, H: int, scale: float, cos_
 # The per-row decode forms and the packed K/V store (generate_ragged) are resolved the same way, for the same reason.
 _PACKED = ("SeqPlan", "attn_seq_plan", "rope_pos_", "attn_fwd_seqs", "attn_bwd_seqs",
            "kv_append_rows", "attn_decode_rows", "attn_decode_append_rows", "kv_store_seqs")
+# ... and so are the projections of a decode batch of 65 to 256 rows (ops_wide.py; stand-ins in tests/emu_wide.py)
+_WIDE = ("gemm_skinny_wide", "skinny_wide_ok", "decode_wide_enabled")
 
 
 def __getattr__(name: str):
     if name in _PACKED:
         from . import ops_packed
         return getattr(ops_packed, name)
+    if name in _WIDE:
+        from . import ops_wide
+        return getattr(ops_wide, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

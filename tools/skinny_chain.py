@@ -3,6 +3,9 @@
 of launches in a captured hipGraph, each launch reading what the previous one wrote (64 rows, bf16).  `cold` chains walk through
 ~600 MB of distinct weight matrices (the event-level stack: 403 MB per decode step, more than the Infinity Cache keeps), `warm`
 chains cycle through three (the token-level stack: 51 MB re-read eight times per event).
+ROWS=1: the six projections of a decode step at 128 and 256 rows on mh_gemm_skinny_wide, with mh_gemm at the same row count (the
+general form's projection: no folded norm, gate|up as the plain 2N-column product without SwiGLU -- its norm and SwiGLU launches are
+NOT in its figure) and the narrow kernel at 64 rows beside them.
 Usage: python tools/skinny_chain.py [launches=96]"""
 import os
 import sys
@@ -22,9 +25,12 @@ def weights(rows, K, n):
     return [(torch.randn((rows, K), device=dev) * (K ** -0.5)).to(torch.bfloat16) for _ in range(n)]
 
 
-def chain(name, N, K, mode, rstd, res, cold, ld_out=None):
-    """a chain of L launches out[64, N] = f(in[64, :K] . W^T); the next launch reads the first K columns of out"""
+def chain(name, N, K, mode, rstd, res, cold, ld_out=None, B=B, kind="skinny"):
+    """a chain of L launches out[B, N] = f(in[B, :K] . W^T); the next launch reads the first K columns of out.
+    kind: "skinny" (mh_gemm_skinny), "wide" (mh_gemm_skinny_wide), "gemm" (mh_gemm, the bare product (+ residual))"""
     rows = 2 * N if mode == ops.SKINNY_GATEUP else N
+    if kind == "gemm":
+        N = rows
     per = rows * K * 2
     nmat = max(3, min(L, int(600e6 // per))) if cold else 3
     Ws = weights(rows, K, nmat)
@@ -36,10 +42,12 @@ def chain(name, N, K, mode, rstd, res, cold, ld_out=None):
         for i in range(L):
             src, dst = bufs[i % 3], bufs[(i + 1) % 3]
             a = src[:, :K]
-            ops.gemm_skinny(a, Ws[i % nmat], dst[:, :N], mode=mode, norm_eps=1e-6 if rstd else 0.0,
-                            res=(src[:, :N] if res and N <= src.shape[1] else None))
-            if N < K:  # keep the next launch's input well defined (and dependent): widen by re-reading what was written
-                pass
+            r = src[:, :N] if res and N <= src.shape[1] else None
+            if kind == "gemm":
+                ops.gemm_nt(a, Ws[i % nmat], dst[:, :N], beta=1.0 if r is not None else 0.0, res=r)
+                continue
+            (ops.gemm_skinny_wide if kind == "wide" else ops.gemm_skinny)(a, Ws[i % nmat], dst[:, :N], mode=mode,
+                                                                          norm_eps=1e-6 if rstd else 0.0, res=r)
 
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
@@ -59,12 +67,26 @@ def chain(name, N, K, mode, rstd, res, cold, ld_out=None):
             e1.record()
             torch.cuda.synchronize()
             best = min(best, e0.elapsed_time(e1))
-    print(f"{name:58s} N={N:5d} K={K:5d} {'cold' if cold else 'warm'} ({nmat:3d} matrices of {per / 1e6:5.1f} MB): "
+    print(f"{name:66s} N={N:5d} K={K:5d} {'cold' if cold else 'warm'} ({nmat:3d} matrices of {per / 1e6:5.1f} MB): "
           f"{1e3 * best / L:6.2f} us per dependent launch", flush=True)
     del Ws, bufs
 
 
 P, G = ops.SKINNY_PLAIN, ops.SKINNY_GATEUP
+if os.environ.get("ROWS"):
+    SHAPES = (("q|k|v: folded RMSNorm", 3072, 1024, P, True, False, None), ("o: plain + residual", 1024, 1024, P, False, True, None),
+              ("event gate|up + SwiGLU: folded RMSNorm", 4096, 1024, G, True, False, None),
+              ("event down K = 4096: plain + residual", 1024, 4096, P, False, True, None),
+              ("token gate|up + SwiGLU: folded RMSNorm", 1024, 1024, G, True, False, None),
+              ("lm_head: folded RMSNorm, ragged N", 3406, 1024, P, True, False, 3456))
+    for cold in (False, True):
+        for name, N, K, mode, rstd, res, ld in SHAPES:
+            ld = max(ld or 0, 2 * N if mode == G else N, K)   # (wide enough for mh_gemm's 2N-column gate|up product)
+            chain(f"M= 64 skinny      {name}", N, K, mode, rstd, res, cold, ld, 64, "skinny")
+            for M in (128, 256):
+                chain(f"M={M:3d} skinny_wide {name}", N, K, mode, rstd, res, cold, ld, M, "wide")
+                chain(f"M={M:3d} mh_gemm     {name}", N, K, mode, rstd, res, cold, ld, M, "gemm")
+    sys.exit(0)
 for cold in (False, True):
     chain("o / token down: plain + residual", 1024, 1024, P, False, True, cold)
     chain("q|k|v: folded RMSNorm", 3072, 1024, P, True, False, cold)
