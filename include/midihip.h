@@ -140,6 +140,35 @@ int mh_scale_cols(const void* W, int64_t ldw, const void* w, void* out, int64_t 
 int mh_scale_cols_batched(const int64_t* jobs, int njobs, int K, int dtype, void* stream);
 int mh_gemm_splitk_reduce(const void* workspace, void* C, int64_t ldc, const void* R, int64_t ldr, int64_t M,
                           int64_t N, int splitk, float alpha, float beta, int dtype, void* stream);
+/* ---- grouped weight gradients: up to 8 products over the SAME contraction rows in one launch, no split-K ----------------------
+ * Problem j:  dw[N, K_out] = rd(alpha * dz[Kc, N]^T x[Kc, K_out] + beta * R)   (both operands read as they lie, contraction-major;
+ * R == NULL with beta == 0, or the gradient accumulated so far -- dw itself is fine).  With wnorm != NULL the projection sits
+ * behind a FOLDED RMSNorm and the product is G', the gradient of W' = W (.) w:
+ *   dw = rd(alpha G' (.) wnorm[None, :] + beta R)   and   colpart[b, k] = sum over rows 256 b .. 256 b + 255 of alpha G'[n, k] W[n, k]
+ * (fp32, [mh_wgrad_grouped_fold_blocks(N), K_out]; fold with mh_colsum into the norm weight's gradient) -- what mh_gemm followed by
+ * mh_gemm_splitk_reduce_fold computes, on ONE fp32 chain per element instead of a sum of slice partials.  A 256 x 256 tile of an
+ * output is one workgroup that contracts all Kc rows; problems are laid out one after the other over the workgroups, so the launch
+ * fills the chip when the tile counts add up to a multiple of the CU count.  A plain problem's result is bit-identical to
+ * mh_gemm(dz, lddz, 1, x, ldx, 1, dw, lddw, R, ldr, N, K_out, Kc, alpha, beta, MH_BF16, 1, NULL, stream) on it alone; every
+ * sum has a fixed order (no atomics).  bf16, production GEMM kernel; operand constraints as mh_gemm with transA = transB = 1; the
+ * fold epilogue also needs K_out, lddw, ldw, ldr multiples of 8 and 16-byte aligned dw, W, wnorm, R, colpart.  `p` is HOST memory,
+ * read before the call returns. */
+typedef struct {
+  const void* dz;  int64_t lddz;
+  const void* x;   int64_t ldx;
+  void* dw;        int64_t lddw;
+  const void* R;   int64_t ldr;
+  int64_t N, K_out;
+  float alpha, beta;
+  const void* wnorm;          /* NULL: plain epilogue */
+  const void* W;   int64_t ldw;
+  float* colpart;
+} mh_wgrad_problem;
+int mh_wgrad_grouped_fold_blocks(int64_t N);
+int mh_gemm_wgrad_grouped(const mh_wgrad_problem* p, int n, int64_t Kc, int dtype, void* stream);
+/* the launch's work-item table seen from the host: (problem, tile row, tile column) of workgroup `lin`; returns the launch's
+ * number of workgroups (-1: bad arguments).  No device is touched. */
+int mh_wgrad_grouped_item(const mh_wgrad_problem* p, int n, int lin, int* problem, int* tm, int* tn);
 /* Skinny projection of the decode step (replaces the per-token nn.Linear calls of LlamaAttention / LlamaMLP /
  * lm_head when q_len == 1, modeling_llama.py:243-281, 174-176; midi_model.py:135): 1 <= M <= 64 rows, bf16.
  *   MH_SKINNY_PLAIN   C[M,N] = A[M,K] * W[N,K]^T (+ R)

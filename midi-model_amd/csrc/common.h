@@ -246,7 +246,7 @@ __device__ inline void glds16(const void* src, void* lds_rows8) {
 // those tiles share GM A-panels and a few B-panels instead of one A-panel and EVERY B-panel (r01 PMC: the
 // row-major order re-streamed the whole 16 MiB weight for every 128-row panel of a [32768x8192x1024] GEMM,
 // 4.2 GB of L2 misses, L2 hit rate 49 %).
-__device__ inline void gemm_tile_of(int idx, int tiles_m, int tiles_n, int GM, int& tm, int& tn) {
+__host__ __device__ inline void gemm_tile_of(int idx, int tiles_m, int tiles_n, int GM, int& tm, int& tn) {
   const int width = GM * tiles_n;
   const int gid = idx / width;
   const int first = gid * GM;

@@ -444,15 +444,70 @@ __device__ __forceinline__ void p8_main_loop(char* smem, const bf16* __restrict_
 //       the product is multiplied by aux[m] = rstd[m] before the epilogue's own arithmetic.  Wave 0 brings the tile's 256 values
 //       into LDS with ONE LDS-DMA request ahead of the main loop's (the oldest request: the first counted wait covers it), so
 //       the epilogue reads them with eight ds_read_b32 and no global latency.
-template <bool TA, bool TB, int ABL, int EPI, int ML, int NRM>
+//
+// GRP (the grouped weight-gradient launch, mh_gemm_wgrad_grouped): ONE launch computes up to GRP_MAX independent products that
+// contract over the same K rows (a layer's four weight gradients: 128 + 64 + 48 + 16 tiles = the 256 CUs, one tile each, the whole
+// contraction in the tile -- no split-K, no fp32 partials, no reduction launch).  A work item finds its problem in a small table
+// that travels in the kernel arguments (grp_item_of: the XCD-contiguous item order, problems one after the other, each in the
+// grouped raster order), takes that problem's operands in place of the kernel's own arguments and then runs the unchanged
+// K-step-32 loop over [0, K) and the unchanged plain epilogue -- so a problem's tiles are the bits mh_gemm(splitk = 1) gives
+// it -- or, for a projection behind a folded RMSNorm (wnorm != NULL), the fold epilogue at the end of this kernel.  No workgroup
+// waits on another and there are no atomics: every sum is one fixed chain.
+constexpr int GRP_MAX = 8;
+struct GrpProblem {
+  const bf16* A;      // d z [K, M] (contraction-major: the rows of the output are its columns)
+  const bf16* B;      // x   [K, N]
+  bf16* C;            // dW  [M, N]
+  const bf16* R;      // beta != 0: the gradient accumulated so far
+  const bf16* wnorm;  // fold epilogue: the norm weight [N]; NULL = plain epilogue
+  const bf16* W;      // fold epilogue: the projection weight [M, N]
+  float* colpart;     // fold epilogue: [tiles_m, N] column sums of alpha G (.) W per 256-row block
+  int64_t lda, ldb, ldc, ldr, ldw, M, N;
+  float alpha, beta;
+  int tile0, tiles_n;  // first work item of the problem; its tile columns
+};
+struct GrpTable {
+  GrpProblem p[GRP_MAX];
+  int n, nitems;
+};
+// work item of workgroup `lin`: the hardware deals workgroups to the 8 XCDs round robin; XCD x takes a CONTIGUOUS range of
+// items (see "Work item order" in the kernel), so the ~32 tiles resident on an XCD are neighbours of one problem
+__host__ __device__ inline int xcd_item_of(int lin, int nitems) {
+  const int q = nitems >> 3, r8 = nitems & 7, xcd = lin & 7;
+  return (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (lin >> 3);
+}
+// -> the problem of workgroup `lin` and its tile there
+__host__ __device__ inline int grp_item_of(const GrpTable& t, int lin, int& tm, int& tn) {
+  const int item = xcd_item_of(lin, t.nitems);
+  int pi = 0;
+#pragma unroll
+  for (int j = 1; j < GRP_MAX; ++j)
+    if (j < t.n && item >= t.p[j].tile0) pi = j;
+  const int tiles_n = t.p[pi].tiles_n;
+  const int tiles_m = (int)((t.p[pi].M + QBM - 1) / QBM);
+  gemm_tile_of(item - t.p[pi].tile0, tiles_m, tiles_n, 4, tm, tn);
+  return pi;
+}
+template <bool GRP>
+struct GrpArg {
+  typedef int type;  // (every other instantiation: an unused word)
+};
+template <>
+struct GrpArg<true> {
+  typedef GrpTable type;
+};
+
+template <bool TA, bool TB, int ABL, int EPI, int ML, int NRM, bool GRP = false>
 __global__ __launch_bounds__(512, 2) void gemm_pp256_kernel(const bf16* __restrict__ A, int64_t lda,
                                                             const bf16* __restrict__ B, int64_t ldb, bf16* C, int64_t ldc,
                                                             const bf16* R, int64_t ldr, int64_t M, int64_t N, int64_t K,
                                                             float alpha, float beta, int tiles_n, int nwg,
                                                             int64_t k_per_split, float* __restrict__ ws,
-                                                            const void* __restrict__ zero16, float* aux, int lean_epi) {
+                                                            const void* __restrict__ zero16, float* aux, int lean_epi,
+                                                            const typename GrpArg<GRP>::type gtab) {
   static_assert(NRM == 0 || (ML == 1 && ABL == 0 && !TA && (!TB || (EPI == 1 && NRM == 2))), "the norm forms ride on the K-step-64 loops only");
   static_assert(NRM != 1 || EPI == 0, "sum-of-squares partials come out of the plain epilogue");
+  static_assert(!GRP || (TA && TB && ABL == 0 && EPI == 0 && ML == 0 && NRM == 0), "the grouped launch is the weight-gradient form");
   // (r06: the row scale also on the plain epilogue -- the token-level q|k|v projection of the folded training forward -- and on the
   //  SwiGLU-backward epilogue, which then delivers d z = rstd (.) d gate|up, the gradient of the UNSCALED product x W'^T: the
   //  operand both the folded dgrad and the folded weight gradient take; engine.layer_backward_folded)
@@ -470,13 +525,22 @@ __global__ __launch_bounds__(512, 2) void gemm_pp256_kernel(const bf16* __restri
   // K-slice in grouped raster order (gemm_tile_of): the ~32 workgroups resident on an XCD then share A/B panels.
   // Without the slice-major part the 16 slices of a [1024 x 1024 x 262144] weight gradient put every tile of a slice
   // on a different XCD and the kernel ran at the HBM/fabric rate (r01: LDS-DMA alone 529 us of 608 us).
-  const int nitems = nwg * (int)gridDim.z;
-  const int lin = blockIdx.x + nwg * (int)blockIdx.z;
-  const int q = nitems >> 3, r8 = nitems & 7, xcd = lin & 7;
-  const int item = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (lin >> 3);
-  const int zslice = item / nwg;
-  int tm, tn;
-  gemm_tile_of(item - zslice * nwg, nwg / tiles_n, tiles_n, 4, tm, tn);
+  int zslice = 0, tm, tn;
+  const bf16 *wnorm = nullptr, *Wf = nullptr;  // GRP, fold epilogue
+  float* colpart = nullptr;
+  int64_t ldw = 0;
+  if constexpr (GRP) {  // the problem's operands take the place of the kernel's own arguments (K, k_per_split: the launcher's)
+    const GrpProblem& P = gtab.p[grp_item_of(gtab, (int)blockIdx.x, tm, tn)];
+    A = P.A, lda = P.lda, B = P.B, ldb = P.ldb, C = P.C, ldc = P.ldc, R = P.R, ldr = P.ldr, M = P.M, N = P.N;
+    alpha = P.alpha, beta = P.beta;
+    wnorm = P.wnorm, Wf = P.W, ldw = P.ldw, colpart = P.colpart;
+  } else {
+    const int nitems = nwg * (int)gridDim.z;
+    const int lin = blockIdx.x + nwg * (int)blockIdx.z;
+    const int item = xcd_item_of(lin, nitems);
+    zslice = item / nwg;
+    gemm_tile_of(item - zslice * nwg, nwg / tiles_n, tiles_n, 4, tm, tn);
+  }
   // EPI == 2 (gate|up projection with the SwiGLU forward as epilogue, mh_gemm_swiglu): B = [gate rows; up rows] (N = 2 I);
   // a tile takes 128 gate rows and the 128 matching up rows, so that every lane ends up holding gate and up of the same
   // output element (wave wn: fragments 0,1 = gate columns wn*32.., fragments 2,3 = the same up columns)
@@ -1024,6 +1088,105 @@ __global__ __launch_bounds__(512, 2) void gemm_pp256_kernel(const bf16* __restri
     }
     return;
   }
+  if constexpr (GRP) {
+    if (wnorm != nullptr) {  // (uniform over the workgroup: every wave of it reaches the barrier below)
+      // Fold epilogue: the chain rule through W' = W (.) w on the tile's fp32 sums, what mh_gemm_splitk_reduce_fold does on the
+      // reduced partials:  dW = rd(alpha G w + beta R)  and  colpart[tm][n] = the sum over the tile's 256 rows of alpha G W.  The
+      // whole-line turn of the general plain form (8 lanes = one 128-byte line of dW, W and R); a lane adds its sixteen rows in
+      // row order, the wave's eight row-lanes are folded by three butterfly steps, then the lower M half adds the upper half's
+      // sums through LDS: one fixed order.  N % 8 == 0, 16-byte aligned lines (launcher).
+      char* wreg = smem + wave * 16384;
+      const int lrow = lane >> 3, c = lane & 7;
+      const int64_t n = n0 + wn * 64 + c * 8;
+      const bool n_ok = (n + 8 <= N);
+      float wnf[8], cs[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) wnf[e] = cs[e] = 0.f;
+      if (n_ok) expand8_bf16(*reinterpret_cast<const bf16x8*>(wnorm + n), wnf);
+      // (one loop per residual choice, as the lean plain form: without R both halves' W lines are requested as soon as the first
+      //  half's sums have left their registers; with R the second half's lines wait for the first half's to be used -- 256 registers)
+      auto turn = [&](auto with_r) {
+        constexpr bool WR = decltype(with_r)::value;
+        bf16x8 wq[2][8], rq[2][8];  // the W (and R) lines of the 64-row halves
+        auto request = [&](int half) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const int64_t m = m0 + grp * 128 + half * 64 + i * 8 + lrow;
+            if (m < M && n_ok) {
+              wq[half][i] = *reinterpret_cast<const bf16x8*>(Wf + m * ldw + n);
+              if constexpr (WR) rq[half][i] = *reinterpret_cast<const bf16x8*>(R + m * ldr + n);
+            }
+          }
+        };
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+#pragma unroll
+          for (int fmh = 0; fmh < 4; ++fmh)
+#pragma unroll
+            for (int fn = 0; fn < 4; ++fn) {
+              const int row = fmh * 16 + fi, ch = fn * 4 + fg;
+              *reinterpret_cast<f32x4*>(wreg + row * 256 + ((ch ^ (row & 15)) << 4)) = acc[fn][half * 4 + fmh];
+            }
+          if (half == 0) request(0);
+          if (half == (WR ? 1 : 0)) request(1);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {  // 8 rows x 128 B per instruction
+            const int row = i * 8 + lrow;
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(wreg + row * 256 + (((2 * c) ^ (row & 15)) << 4));
+            const f32x4 hi = *reinterpret_cast<const f32x4*>(wreg + row * 256 + (((2 * c + 1) ^ (row & 15)) << 4));
+            const int64_t m = m0 + grp * 128 + half * 64 + row;
+            if (m >= M || !n_ok) continue;
+            float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            float wf[8];
+            expand8_bf16(wq[half][i], wf);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              v[e] = alpha * v[e];
+              cs[e] += v[e] * wf[e];
+              v[e] *= wnf[e];
+            }
+            if constexpr (WR) {
+              float rf[8];
+              expand8_bf16(rq[half][i], rf);
+#pragma unroll
+              for (int e = 0; e < 8; ++e) v[e] += beta * rf[e];
+            }
+            bf16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = (bf16)v[e];
+            __builtin_nontemporal_store(o, reinterpret_cast<bf16x8*>(C + m * ldc + n));
+          }
+        }
+      };
+      if (__builtin_amdgcn_readfirstlane((int)(R != nullptr && beta != 0.f))) turn(std::true_type{});
+      else turn(std::false_type{});
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {  // the eight row-lanes lrow = 0..7 of column chunk c (lanes c + 8 lrow)
+        cs[e] += __shfl_xor(cs[e], 8);
+        cs[e] += __shfl_xor(cs[e], 16);
+        cs[e] += __shfl_xor(cs[e], 32);
+      }
+      // (the upper M half's wave of these 64 columns hands its sums over in its own turn region, as the type the turn uses)
+      f32x4* half_sums = reinterpret_cast<f32x4*>(smem + (wn + 4) * 16384) + c * 2;
+      if (grp == 1 && lrow == 0) {
+        half_sums[0] = f32x4{cs[0], cs[1], cs[2], cs[3]};
+        half_sums[1] = f32x4{cs[4], cs[5], cs[6], cs[7]};
+      }
+      __syncthreads();
+      if (grp == 0 && lrow == 0 && n_ok) {
+        f32x4 s0 = half_sums[0], s1 = half_sums[1];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          s0[e] = cs[e] + s0[e];
+          s1[e] = cs[4 + e] + s1[e];
+        }
+        float* dst = colpart + (int64_t)tm * N + n;
+        *reinterpret_cast<f32x4*>(dst) = s0;
+        *reinterpret_cast<f32x4*>(dst + 4) = s1;
+      }
+      return;
+    }
+  }
   const bool use_r = (R != nullptr && beta != 0.f);
   const bool line_ok = !partial && (ldc & 7) == 0 && ((uintptr_t)C & 15) == 0 &&
                        (!use_r || ((ldr & 7) == 0 && ((uintptr_t)R & 15) == 0));
@@ -1221,11 +1384,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp256_kernel(const bf16* __restri
 }  // namespace
 extern thread_local int g_mh_gemm_lean_epi;  // api.cpp: option "gemm_lean_epi" (default 1): interior tiles take the r06 forms of the plain / SwiGLU-backward epilogues
 namespace {
-template <bool TA, bool TB, int ABL, int EPI = 0, int ML = 0, int NRM = 0>
-int launch_one(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const void* R, int64_t ldr,
-               int64_t M, int64_t N, int64_t K, float alpha, float beta, int splitk, void* workspace, hipStream_t st,
-               float* aux = nullptr) {
-  constexpr int LDSB = LDS_BYTES + ((ABL & 128) ? P8_DBG_BYTES : 0) + (NRM == 2 ? 1024 : 0);
+// what a launch of instantiation KERNEL needs first: the zero chunk's device address and the kernel's dynamic-LDS limit
+template <auto KERNEL>
+int launch_prepare(int LDSB, void** zero16_out) {
   // Both caches are PER DEVICE (a symbol's address and a function attribute belong to the device that is current when they
   // are asked for): a host that drives several GPUs from one process gets each device's own, keyed by the calling thread's
   // current device -- which is the device of `st`, as for every entry point (include/midihip.h).  Racing first calls write
@@ -1247,14 +1408,24 @@ int launch_one(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, 
     __atomic_store_n(&zero16_of[dev], zero16, __ATOMIC_RELEASE);
   }
   if (!__atomic_load_n(&attr_set_of[dev], __ATOMIC_ACQUIRE)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp256_kernel<TA, TB, ABL, EPI, ML, NRM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);
     if (e != hipSuccess) {
       mh_set_error("gemm_pp256: cannot raise dynamic LDS to %d bytes: %s", LDSB, hipGetErrorString(e));
       return MH_ERR_LAUNCH;
     }
     __atomic_store_n(&attr_set_of[dev], true, __ATOMIC_RELEASE);
   }
+  *zero16_out = zero16;
+  return MH_OK;
+}
+
+template <bool TA, bool TB, int ABL, int EPI = 0, int ML = 0, int NRM = 0>
+int launch_one(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, const void* R, int64_t ldr,
+               int64_t M, int64_t N, int64_t K, float alpha, float beta, int splitk, void* workspace, hipStream_t st,
+               float* aux = nullptr) {
+  constexpr int LDSB = LDS_BYTES + ((ABL & 128) ? P8_DBG_BYTES : 0) + (NRM == 2 ? 1024 : 0);
+  void* zero16 = nullptr;
+  if (int rc = launch_prepare<&gemm_pp256_kernel<TA, TB, ABL, EPI, ML, NRM>>(LDSB, &zero16)) return rc;
   const int64_t tiles_m = (M + QBM - 1) / QBM, tiles_n = (EPI == 2) ? N / 256 : (N + QBN - 1) / QBN;  // (EPI 2: I / 128)
   const int nwg = (int)(tiles_m * tiles_n);
   constexpr int KSTEP = (ML == 1) ? 64 : QBK;
@@ -1262,15 +1433,91 @@ int launch_one(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, 
   dim3 grid(nwg, 1, splitk);
   gemm_pp256_kernel<TA, TB, ABL, EPI, ML, NRM><<<grid, 512, LDSB, st>>>((const bf16*)A, lda, (const bf16*)B, ldb, (bf16*)C, ldc,
                                                           (const bf16*)R, ldr, M, N, K, alpha, beta, (int)tiles_n, nwg, kps,
-                                                          (float*)workspace, zero16, aux, g_mh_gemm_lean_epi);
+                                                          (float*)workspace, zero16, aux, g_mh_gemm_lean_epi, 0);
   MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// the table of a grouped weight-gradient launch from the C-ABI's problem list (validated by the caller)
+void grp_table_of(const mh_wgrad_problem* p, int n, GrpTable& t) {
+  t.n = n;
+  int tile0 = 0;
+  for (int j = 0; j < GRP_MAX; ++j) {
+    GrpProblem& g = t.p[j];
+    if (j >= n) {
+      g = GrpProblem{};
+      g.tile0 = INT_MAX;
+      continue;
+    }
+    g.A = (const bf16*)p[j].dz, g.lda = p[j].lddz, g.B = (const bf16*)p[j].x, g.ldb = p[j].ldx;
+    g.C = (bf16*)p[j].dw, g.ldc = p[j].lddw, g.R = (const bf16*)p[j].R, g.ldr = p[j].ldr;
+    g.wnorm = (const bf16*)p[j].wnorm, g.W = (const bf16*)p[j].W, g.ldw = p[j].ldw, g.colpart = p[j].colpart;
+    g.M = p[j].N, g.N = p[j].K_out, g.alpha = p[j].alpha, g.beta = p[j].beta;
+    g.tile0 = tile0;
+    g.tiles_n = (int)((g.N + QBN - 1) / QBN);
+    tile0 += (int)((g.M + QBM - 1) / QBM) * g.tiles_n;
+  }
+  t.nitems = tile0;
+}
+
+int grp_validate(const mh_wgrad_problem* p, int n, int64_t Kc, int dtype) {
+  MH_REQUIRE(dtype == MH_BF16, "gemm_wgrad_grouped: bf16 only");
+  MH_REQUIRE(p != nullptr && n >= 1 && n <= GRP_MAX && Kc > 0, "gemm_wgrad_grouped: 1 to %d problems and a contraction length (n=%d Kc=%ld)",
+             GRP_MAX, n, (long)Kc);
+  int64_t tiles = 0;
+  for (int j = 0; j < n; ++j) {
+    const mh_wgrad_problem& q = p[j];
+    MH_REQUIRE(q.N > 0 && q.K_out > 0 && q.dz != nullptr && q.x != nullptr && q.dw != nullptr, "gemm_wgrad_grouped: problem %d is empty", j);
+    // (mh_gemm's constraints with both operands contraction-major)
+    MH_REQUIRE(q.lddz % 8 == 0 && q.ldx % 8 == 0 && q.lddz >= q.N && q.ldx >= q.K_out && q.lddw >= q.K_out,
+               "gemm_wgrad_grouped: problem %d: leading dimensions must be multiples of 8 elements and cover the rows", j);
+    MH_REQUIRE((((uintptr_t)q.dz | (uintptr_t)q.x) & 15) == 0, "gemm_wgrad_grouped: problem %d: dz / x must be 16-byte aligned", j);
+    MH_REQUIRE(q.beta == 0.f || (q.R != nullptr && q.ldr >= q.K_out), "gemm_wgrad_grouped: problem %d: beta != 0 needs R", j);
+    if (q.wnorm != nullptr) {
+      MH_REQUIRE(q.W != nullptr && q.colpart != nullptr && q.K_out % 8 == 0 && q.lddw % 8 == 0 && q.ldw % 8 == 0 && q.ldw >= q.K_out &&
+                     (q.R == nullptr || q.ldr % 8 == 0),
+                 "gemm_wgrad_grouped: problem %d: the fold epilogue needs W, colpart and whole 16-byte lines (K_out, lddw, ldw, ldr %% 8 == 0)", j);
+      MH_REQUIRE((((uintptr_t)q.dw | (uintptr_t)q.W | (uintptr_t)q.wnorm | (uintptr_t)q.R | (uintptr_t)q.colpart) & 15) == 0,
+                 "gemm_wgrad_grouped: problem %d: the fold epilogue needs 16-byte aligned dw, W, wnorm, R and colpart", j);
+    }
+    tiles += ((q.N + QBM - 1) / QBM) * ((q.K_out + QBN - 1) / QBN);
+  }
+  MH_REQUIRE(tiles < (1ll << 30), "gemm_wgrad_grouped: too many tiles");
   return MH_OK;
 }
 
 }  // namespace
 
+extern thread_local int g_mh_gemm_variant;  // api.cpp
 extern thread_local int g_mh_gemm_ablate;   // api.cpp
-extern thread_local int g_mh_gemm_k64;      // api.cpp: row-major x row-major products take the K-step-64 main loop (default 1)
+
+extern "C" int mh_wgrad_grouped_fold_blocks(int64_t N) { return (int)(N < 1 ? 1 : (N + QBM - 1) / QBM); }
+
+extern "C" int mh_gemm_wgrad_grouped(const mh_wgrad_problem* p, int n, int64_t Kc, int dtype, void* stream) {
+  if (int rc = grp_validate(p, n, Kc, dtype)) return rc;
+  MH_REQUIRE(g_mh_gemm_variant != 0 && g_mh_gemm_ablate == 0, "gemm_wgrad_grouped: served by the production bf16 kernel only");
+  GrpTable t;
+  grp_table_of(p, n, t);
+  void* zero16 = nullptr;
+  if (int rc = launch_prepare<&gemm_pp256_kernel<true, true, 0, 0, 0, 0, true>>(LDS_BYTES, &zero16)) return rc;
+  const int64_t kps = (Kc + QBK - 1) / QBK * QBK;
+  gemm_pp256_kernel<true, true, 0, 0, 0, 0, true><<<dim3(t.nitems, 1, 1), 512, LDS_BYTES, (hipStream_t)stream>>>(
+      nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, 0, Kc, 1.f, 0.f, 0, t.nitems, kps, nullptr, zero16, nullptr, g_mh_gemm_lean_epi, t);
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// host view of the launch's work-item table (the tile-map test): the (problem, tm, tn) of workgroup `lin`; returns the number of
+// workgroups, or -1 on bad arguments
+extern "C" int mh_wgrad_grouped_item(const mh_wgrad_problem* p, int n, int lin, int* problem, int* tm, int* tn) {
+  if (p == nullptr || n < 1 || n > GRP_MAX) return -1;
+  GrpTable t;
+  grp_table_of(p, n, t);
+  if (lin >= 0 && lin < t.nitems && problem != nullptr && tm != nullptr && tn != nullptr) *problem = grp_item_of(t, lin, *tm, *tn);
+  return t.nitems;
+}
+
+extern thread_local int g_mh_gemm_k64;     // api.cpp: row-major x row-major products take the K-step-64 main loop (default 1)
 
 // called by gemm.hip after argument validation (bf16 only)
 int mh_gemm_pp256_bf16(const void* A, int64_t lda, int ta, const void* B, int64_t ldb, int tb, void* C, int64_t ldc,

@@ -407,7 +407,15 @@ def layer_backward_folded(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, f
     M, D = dx.shape
     H = spec.H
     wq_n, wgu_n = fold
-    dx2, do = _folded_mlp_o_backward(spec, lw, lg, wgu_n, keep, dx, accumulate)
+    # Event-level stack: the block's four weight gradients contract over the same M rows and their 256 x 256 tiles add up to the
+    # CU count at the benchmarked shape, so they wait in ``pend`` (with the operands they keep alive: d z2, a, dx2, d z1) and go
+    # out as ONE grouped launch without split-K (ops.wgrad_grouped).  The token-level stack (112 tiles per layer at a contraction
+    # of 8 x the rows: split-K fills the chip, a group would not) and the packed-batch path keep one launch per gradient.
+    I = spec.I
+    pend = None
+    if spec.kind == "event" and seqs is None and ops.wgrad_grouped_ok([(D, I), (2 * I, D), (D, D), (3 * D, D)], M, dx):
+        pend = []
+    dx2, do = _folded_mlp_o_backward(spec, lw, lg, wgu_n, keep, dx, accumulate, pend)
     dz1 = _empty((M, 3 * D), dx)
     if seqs is not None:
         ops.attn_bwd_seqs(keep.qkv, keep.o, do, keep.lse, dz1, seqs, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
@@ -417,16 +425,23 @@ def layer_backward_folded(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, f
         ops.tokattn_bwd(keep.qkv, do, dz1, nseq, slen, H, spec.scale, rope.cos, rope.sin, rowscale=keep.rstd1)
     t1 = do
     ops.gemm_nt(dz1, wq_n, t1, tb=True)                      # t1 = d z1 @ W'qkv
-    ops.wgrad_folded(dz1, keep.x, lg.wqkv, lw.n1, lw.wqkv, lg.n1, accumulate)
+    if pend is not None:
+        pend.append((dz1, keep.x, lg.wqkv, (lw.n1, lw.wqkv, lg.n1)))
+        ops.wgrad_grouped(pend, accumulate)                  # (before the norm backward below overwrites dx, the down projection's operand)
+        pend.clear()
+    else:
+        ops.wgrad_folded(dz1, keep.x, lg.wqkv, lw.n1, lw.wqkv, lg.n1, accumulate)
     del dz1
     ops.rmsnorm_bwd_folded(keep.x, keep.rstd1, t1, dx2, dx)
     return dx
 
 
 def _folded_mlp_o_backward(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, wgu_n: torch.Tensor, keep: LayerSaved,
-                           dx: torch.Tensor, accumulate: bool):
+                           dx: torch.Tensor, accumulate: bool, pend: Optional[list] = None):
     """The folded block's backward from its output down to the attention: the MLP half, then the o projection.
-    Returns (dx2 = the gradient of the residual stream between the halves, do = the gradient of the attention output)."""
+    Returns (dx2 = the gradient of the residual stream between the halves, do = the gradient of the attention output).
+    ``pend`` (a list): the three weight gradients are not launched but appended to it as ops.wgrad_grouped problems; the caller
+    launches them before it overwrites ``dx``."""
     M, D = dx.shape
     I = spec.I
     # ---- MLP ----
@@ -436,18 +451,27 @@ def _folded_mlp_o_backward(spec: StackSpec, lw: LayerTensors, lg: LayerTensors, 
         ops.swiglu_fwd(keep.gu, a)
     dz2 = _empty((M, 2 * I), dx)
     ops.gemm_dswiglu(dx, lw.wd, keep.gu, dz2, rowscale=keep.rstd2)     # rstd2 (.) SwiGLU'(gate|up) (dx @ wd)
-    linear_wgrad(dx, a, lg.wd, accumulate)
+    if pend is not None:
+        pend.append((dx, a, lg.wd, None))
+    else:
+        linear_wgrad(dx, a, lg.wd, accumulate)
     del a
     t2 = _empty((M, D), dx)
     ops.gemm_nt(dz2, wgu_n, t2, tb=True)                     # t2 = d z2 @ W'gu
-    ops.wgrad_folded(dz2, keep.x2, lg.wgu, lw.n2, lw.wgu, lg.n2, accumulate)
+    if pend is not None:
+        pend.append((dz2, keep.x2, lg.wgu, (lw.n2, lw.wgu, lg.n2)))
+    else:
+        ops.wgrad_folded(dz2, keep.x2, lg.wgu, lw.n2, lw.wgu, lg.n2, accumulate)
     del dz2
     dx2 = _empty((M, D), dx)
     ops.rmsnorm_bwd_folded(keep.x2, keep.rstd2, t2, dx, dx2)
     # ---- attention ----
     do = t2                                                  # reuse
     ops.gemm_nt(dx2, lw.wo, do, tb=True)
-    linear_wgrad(dx2, keep.o, lg.wo, accumulate)
+    if pend is not None:
+        pend.append((dx2, keep.o, lg.wo, None))
+    else:
+        linear_wgrad(dx2, keep.o, lg.wo, accumulate)
     return dx2, do
 
 

@@ -507,6 +507,13 @@ def wgrad_folded(dz: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, wnorm: tor
     M = dz.shape[0]
     N, K = dw.shape
     assert dz.shape[1] == N and x.shape == (M, K) and W.shape == (N, K) and wnorm.shape == (K,) and dnorm.shape == (K,)
+    if _pick_splitk(N, K, M) == 1:
+        # no slices wanted (the tiles fill the chip, or the contraction is short): the fold rides in the GEMM's own epilogue
+        # (the grouped launch with one problem) -- no fp32 partials written and read back, no reduction launch
+        from . import ops_grouped
+        if ops_grouped.wgrad_grouped_operands_ok([(dz, x, dw, (wnorm, W, dnorm))]):
+            ops_grouped.wgrad_grouped([(dz, x, dw, (wnorm, W, dnorm))], accumulate)
+            return
     splitk = max(2, _pick_splitk(N, K, M))   # (the fold's chain rule lives in the reduction: always at least two slices)
     ws = torch.empty((splitk, N, K), dtype=torch.float32, device=dw.device)
     prof = gemm_profile
@@ -598,9 +605,14 @@ _PACKED = ("SeqPlan", "attn_seq_plan", "rope_pos_", "attn_fwd_seqs", "attn_bwd_s
            "kv_append_rows", "attn_decode_rows", "attn_decode_append_rows", "kv_store_seqs")
 # ... and so are the projections of a decode batch of 65 to 256 rows (ops_wide.py; stand-ins in tests/emu_wide.py)
 _WIDE = ("gemm_skinny_wide", "skinny_wide_ok", "decode_wide_enabled")
+# ... and the grouped weight-gradient launch (ops_grouped.py; the emulation never takes it: it asks for device tensors)
+_GROUPED = ("wgrad_grouped", "wgrad_grouped_ok", "wgrad_grouped_operands_ok", "wgrad_grouped_enabled", "wgrad_grouped_launches")
 
 
 def __getattr__(name: str):
+    if name in _GROUPED:
+        from . import ops_grouped
+        return getattr(ops_grouped, name)
     if name in _PACKED:
         from . import ops_packed
         return getattr(ops_packed, name)
