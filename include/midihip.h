@@ -503,6 +503,20 @@ int mh_sample_top_p_k(const void* logits, int64_t ldl, const uint8_t* first_mask
                       int pos, const float* q, int64_t* out,
                       int64_t out_stride, int64_t* out_b, int64_t* out_c, int64_t B, int V, float temp, float top_p,
                       int top_k, int fill_rest, int64_t fill_id, int dtype, void* stream);
+/* The per-row form of mh_sample_top_p_k (generate_ragged with a parameter set per row): `temp`, `top_p` (float) and `top_k`
+ * (int32) are DEVICE arrays [B], required, and always read on the device -- one scalar load each per workgroup, as the per-row
+ * decode kernels read row_pos -- so a captured graph serves every setting.  Each mask comes with a byte stride: row b reads
+ * first_mask + b * first_stride and ban_mask + b * ban_stride, V bytes each; stride 0 = one mask for all rows.  first_lo /
+ * first_hi stay host-stated facts and must span EVERY row's first mask.  Row b computes exactly what mh_sample_top_p_k computes
+ * when launched with temp[b], top_p[b], top_k[b] and row b's masks: the same kernel, the same arithmetic in the same order, the
+ * same id.  The caller validates the values (temp > 0 and finite, 1 <= top_k <= min(64, V)); the kernel clamps top_k[b] into
+ * that range before any use, so no array content makes it read or write out of bounds.  Everything else as above.            */
+int mh_sample_top_p_k_rows(const void* logits, int64_t ldl, const uint8_t* first_mask, int64_t first_stride,
+                           const uint8_t* ban_mask, int64_t ban_stride, int first_lo, int first_hi,
+                           const int32_t* lo_tab, const int32_t* hi_tab, int tab_stride, int max_range, const int64_t* ev,
+                           int pos, const float* q, int64_t* out, int64_t out_stride, int64_t* out_b, int64_t* out_c,
+                           int64_t B, int V, const float* temp, const float* top_p, const int32_t* top_k, int fill_rest,
+                           int64_t fill_id, int dtype, void* stream);
 
 /* ---- the data-parallel gradient exchange on RCCL (reference: DDP under Lightning, train.py:461-474) -----------------
  * One communicator per process/GPU.  librccl is opened on the first call (dlopen; not a link-time dependency).

@@ -573,7 +573,25 @@ constexpr int SAMPLE_MAX_RANGE = 2048;
 // the eight token positions) are ranked by counting (each lane compares its two candidates with all 128 through v_readlane)
 // instead of top_k rounds of a wave-wide arg-max; the cumulative top-p filter and the final argmax(p / q) run with one rank
 // per lane, the sums in the reference's sequential order.
-template <typename T, int TMAX>  // TMAX: candidates per lane (64 * TMAX >= the longest mask range of this position)
+//
+// ROWS (mh_sample_top_p_k_rows; generate_ragged with per-row parameters): temperature, top-p and top-k are DEVICE arrays [B] and
+// each mask has a byte stride per row.  One block owns one row (blockIdx.x), so the three values are block-uniform: one scalar
+// load each per workgroup, issued right behind the argument fetch, and everything below the loads is the uniform form's code -- same
+// arithmetic in the same order, same id.  top_k[b] is clamped into [1, min(SAMPLE_MAX_K, V)] before any use (the q row read,
+// sel_v / sel_i / wl, the readlane loops): whatever the arrays hold, no access leaves its buffer.  The two strides are read by
+// ROWS instantiations only.
+template <bool ROWS>
+struct SampleArg {  // how the kernel receives temp / top_p / top_k: by value, or per row from device memory
+  using F = float;
+  using I = int;
+};
+template <>
+struct SampleArg<true> {
+  using F = const float* __restrict__;
+  using I = const int32_t* __restrict__;
+};
+
+template <typename T, int TMAX, bool ROWS = false>  // TMAX: candidates per lane (64 * TMAX >= the longest mask range of this position)
 __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict__ logits, int64_t ldl,
                                                              const uint8_t* __restrict__ first_mask,
                                                              const uint8_t* __restrict__ ban_mask,
@@ -583,8 +601,11 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
                                                              int first_hi, const float* __restrict__ q,
                                                              int64_t* __restrict__ out, int64_t out_stride,
                                                              int64_t* __restrict__ out_b, int64_t* __restrict__ out_c,
-                                                             int64_t B, int V, float temp, float top_p, int top_k,
-                                                             int fill_rest, int64_t fill_id) {
+                                                             int64_t B, int V, typename SampleArg<ROWS>::F temp_arg,
+                                                             typename SampleArg<ROWS>::F top_p_arg,
+                                                             typename SampleArg<ROWS>::I top_k_arg, int fill_rest,
+                                                             int64_t fill_id, int64_t first_stride = 0,
+                                                             int64_t ban_stride = 0) {
   __shared__ float sel_v[SAMPLE_MAX_K];
   __shared__ int sel_i[SAMPLE_MAX_K];
   __shared__ float part_m[4], part_s[4];
@@ -597,9 +618,30 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
   // (every kernel argument fetched at entry in one batch: see attn_decode_kernel)
   asm volatile("" ::"s"(logits), "s"(ldl), "s"(first_mask), "s"(ban_mask), "s"(lo_tab), "s"(hi_tab), "s"(tab_stride), "s"(ev));
   asm volatile("" ::"s"(pos), "s"(first_lo), "s"(first_hi), "s"(q), "s"(out), "s"(out_stride), "s"(out_b), "s"(out_c));
-  asm volatile("" ::"s"(V), "s"(temp), "s"(top_p), "s"(top_k), "s"(fill_rest), "s"(fill_id));
+  asm volatile("" ::"s"(V), "s"(temp_arg), "s"(top_p_arg), "s"(top_k_arg), "s"(fill_rest), "s"(fill_id));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t b = blockIdx.x;
+  float temp, top_p;
+  int top_k;
+  if constexpr (ROWS) {
+    asm volatile("" ::"s"(first_stride), "s"(ban_stride));
+    // this row's values.  Read through the constant address space: the kernel never writes the three arrays, and that is what
+    // makes hipcc emit s_load_dword for a block-uniform address (a plain const __restrict__ read compiles to a vector load on
+    // every lane + v_readfirstlane)
+    typedef const __attribute__((address_space(4))) float* ConstF;
+    typedef const __attribute__((address_space(4))) int32_t* ConstI;
+    temp = *(ConstF)(uintptr_t)(temp_arg + b);
+    top_p = *(ConstF)(uintptr_t)(top_p_arg + b);
+    top_k = *(ConstI)(uintptr_t)(top_k_arg + b);
+    const int kmax = V < SAMPLE_MAX_K ? V : SAMPLE_MAX_K;
+    top_k = top_k < 1 ? 1 : (top_k > kmax ? kmax : top_k);
+    first_mask += b * first_stride;
+    ban_mask += b * ban_stride;
+  } else {
+    temp = temp_arg;
+    top_p = top_p_arg;
+    top_k = top_k_arg;
+  }
   const T* row = logits + b * ldl;
   // ---- wave 0: everything that does not need the softmax statistics, requested first
   float qv = 1.f, zc[TW];
@@ -841,6 +883,38 @@ extern "C" int mh_sample_top_p_k(const void* logits, int64_t ldl, const uint8_t*
   else if (span <= 512) MH_SAMPLE(8);
   else MH_SAMPLE(32);
 #undef MH_SAMPLE
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// The per-row form: temp / top_p / top_k are device arrays [B], always read on the device; row b's masks start b * stride bytes
+// behind the mask pointers (stride 0: one mask for all rows).
+extern "C" int mh_sample_top_p_k_rows(const void* logits, int64_t ldl, const uint8_t* first_mask, int64_t first_stride,
+                                      const uint8_t* ban_mask, int64_t ban_stride, int first_lo, int first_hi,
+                                      const int32_t* lo_tab, const int32_t* hi_tab, int tab_stride, int max_range,
+                                      const int64_t* ev, int pos, const float* q, int64_t* out, int64_t out_stride,
+                                      int64_t* out_b, int64_t* out_c, int64_t B, int V, const float* temp, const float* top_p,
+                                      const int32_t* top_k, int fill_rest, int64_t fill_id, int dtype, void* stream) {
+  MH_REQUIRE(B > 0 && V > 0 && pos >= 0 && pos < tab_stride && fill_rest >= 0 && fill_rest < out_stride,
+             "sample_top_p_k_rows: bad args");
+  MH_REQUIRE(temp != nullptr && top_p != nullptr && top_k != nullptr,
+             "sample_top_p_k_rows: temp, top_p (float [B]) and top_k (int32 [B]) are device arrays and required");
+  MH_REQUIRE(first_mask != nullptr && ban_mask != nullptr && q != nullptr,
+             "sample_top_p_k_rows: first_mask, ban_mask (V bytes per row; all zero = nothing banned) and q are required");
+  MH_REQUIRE(first_stride >= 0 && ban_stride >= 0, "sample_top_p_k_rows: negative mask stride");
+  MH_REQUIRE(pos == 0 || (ev != nullptr && lo_tab != nullptr && hi_tab != nullptr), "sample_top_p_k_rows: position %d needs the event ids and range tables", pos);
+  MH_REQUIRE(first_lo >= 0 && first_hi <= V && first_hi - first_lo <= SAMPLE_MAX_RANGE && max_range <= SAMPLE_MAX_RANGE,
+             "sample_top_p_k_rows: a grammar mask spans more than %d ids (first %d..%d, parameters %d)", SAMPLE_MAX_RANGE,
+             first_lo, first_hi, max_range);
+  const int span = pos == 0 ? first_hi - first_lo : max_range;
+#define MH_SAMPLE_ROWS(TMAX_)                                                                                             \
+  DISPATCH_T(dtype, (sample_top_p_k_kernel<T, TMAX_, true><<<(int)B, 256, 0, (hipStream_t)stream>>>(                     \
+                        (const T*)logits, ldl, first_mask, ban_mask, lo_tab, hi_tab, tab_stride, ev, pos, first_lo, first_hi, q, out, \
+                        out_stride, out_b, out_c, B, V, temp, top_p, top_k, fill_rest, fill_id, first_stride, ban_stride)))
+  if (span <= 128) MH_SAMPLE_ROWS(2);
+  else if (span <= 512) MH_SAMPLE_ROWS(8);
+  else MH_SAMPLE_ROWS(32);
+#undef MH_SAMPLE_ROWS
   MH_LAUNCH_CHECK();
   return MH_OK;
 }

@@ -21,8 +21,9 @@ tests) keep the step-by-step form: one graph / call per token step with the refe
 
 The graphs are hipGraphs captured through torch.cuda.CUDAGraph from the same Python schedule the eager path runs
 (``engine.stack_decode``), so there is one implementation of the step.  A session owns every buffer the graphs touch and
-is keyed by (parameter buffer, batch, capacity, temperature, top_p, top_k); ``MIDIModel`` keeps a pool of them and hands one to each
-``generate`` call, so concurrent generators on one model (app.py:496) never share scratch.
+is keyed by (parameter buffer, batch, capacity, temperature, top_p, top_k) -- a ``row_params`` session, below, by the first
+three alone; ``MIDIModel`` keeps a pool of them and hands one to each ``generate`` call, so concurrent generators on one model
+(app.py:496) never share scratch.
 
 ``shared_capacity`` > 0 (generate(share_prompt=True), shared.py): the B rows continue ONE prompt.  ``kvp`` (one sequence,
 shared_capacity rows) holds the prompt's K/V, ``kv1`` only the generated suffix, a device int32 ``pre_len`` sits beside ``pos``,
@@ -35,6 +36,13 @@ the net body advances it on the device as pos = min(pos + 1, pos_limit), pos_lim
 max_len is PARKED there, keeps overwriting cache row max_len (capacity max_len + 1, the plain rule) and keeps being sampled; the
 host drops what it samples.  No per-row host state, no extra sync; the graphs' geometry depends on B and the capacity only, so
 one pooled session serves any mix of lengths.  The token level, the sampler and the noise graph are row-uniform and unchanged.
+
+``row_params`` (ragged only; generate_ragged with a value per row): temperature, top-p, top-k, the two masks and the parking position
+live in session buffers with one entry per row -- ``temp_rows``, ``top_p_rows``, ``top_k_rows`` [B], ``first_mask`` and ``ban`` [B, V],
+``pos_limit`` [B] -- and the token steps call mh_sample_top_p_k_rows, which reads them on the device.  The captured graphs hold
+addresses, not values, and the pool key holds no sampling parameter: one session serves every setting of its (B, capacity), and
+a new setting is B-element copies (set_row_params, set_limit) instead of a new K/V cache and three captures.  The form has no
+op-by-op sampler behind it: it needs the fused kernel (grammar spans of at most 2048 ids, top_k <= 64).
 """
 from __future__ import annotations
 
@@ -42,6 +50,7 @@ import os
 import threading
 from typing import List, Optional
 
+import numpy as np
 import torch
 
 from . import engine, ops
@@ -66,13 +75,14 @@ def graphs_enabled(device: torch.device) -> bool:
 
 class DecodeSession:
     def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int, shared_capacity: int = 0,
-                 ragged: bool = False):
+                 ragged: bool = False, row_params: bool = False):
         tok = model.tokenizer
         self.model, self.B, self.cap, self.temp = model, B, capacity, float(temp)
         self.top_p, self.top_k = float(top_p), int(top_k)
         self.shared_capacity = int(shared_capacity)
         self.ragged = bool(ragged)
-        self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged)
+        self.row_params = bool(row_params)
+        self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params)
         dev, dt = model.device, model.dtype
         self.T, self.V, self.Vp = tok.max_token_seq, tok.vocab_size, model.vocab_padded
         spec, tspec = model._specs["net"], model._specs["net_token"]
@@ -94,9 +104,20 @@ class DecodeSession:
         self.first_span, self.max_range = ops.mask_spans(first, lo, hi)  # (generate() only ever clears bits of first_mask)
         self.fused_sampler = (1 <= self.top_k <= min(ops.SAMPLE_MAX_K, self.V) and max(self.max_range) <= ops.SAMPLE_MAX_RANGE
                               and self.first_span[1] - self.first_span[0] <= ops.SAMPLE_MAX_RANGE)
+        self.temp_rows = self.top_p_rows = self.top_k_rows = None
+        if self.row_params:
+            if not self.fused_sampler:
+                raise ValueError(f"DecodeSession(row_params=True) needs the fused sampler: top_k {self.top_k} outside [1, "
+                                 f"{min(ops.SAMPLE_MAX_K, self.V)}] or a grammar mask of more than {ops.SAMPLE_MAX_RANGE} ids")
+            # one entry per row at fixed addresses (the arguments fill them until set_row_params / generate_ragged does)
+            self.temp_rows = torch.full((B,), self.temp, dtype=torch.float32, device=dev)
+            self.top_p_rows = torch.full((B,), self.top_p, dtype=torch.float32, device=dev)
+            self.top_k_rows = torch.full((B,), self.top_k, dtype=torch.int32, device=dev)
+            self.first_mask = first[None, :].repeat(B, 1)
+            self.ban = torch.zeros_like(self.first_mask)
         # cached events so far (device side); ragged: per row, and the position a row is parked at (the call's max_len)
         self.pos = torch.zeros(B if self.ragged else 1, dtype=torch.int32, device=dev)
-        self.pos_limit = torch.zeros(1, dtype=torch.int32, device=dev) if self.ragged else None
+        self.pos_limit = torch.zeros(B if self.row_params else 1, dtype=torch.int32, device=dev) if self.ragged else None
         self.hidden = torch.zeros((B, spec.D), dtype=dt, device=dev)
         self.seq = torch.zeros((B, self.T), dtype=torch.long, device=dev)  # tokens of the event being sampled
         self.samples_in = torch.zeros((B,), dtype=torch.long, device=dev)  # token sampled at the previous position
@@ -137,9 +158,15 @@ class DecodeSession:
             self._capture()
 
     @staticmethod
-    def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False):
+    def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False, row_params=False):
         if ragged and shared_capacity:
             raise ValueError("DecodeSession: ragged rows have prompts of their own -- not together with a shared prompt")
+        if row_params:
+            if shared_capacity or not ragged:
+                raise ValueError("DecodeSession: row_params is a form of the ragged session -- not with a shared prompt, not "
+                                 "without ragged=True")
+            # no temperature, top-p or top-k: they are buffer contents of this form, not facts of its graphs
+            return (model._flat.data_ptr(), model._flat.dtype, B, capacity, ("ragged", "row_params"))
         key = (model._flat.data_ptr(), model._flat.dtype, B, capacity, float(temp), float(top_p), int(top_k))
         if ragged:
             return key + (("ragged",),)
@@ -212,6 +239,12 @@ class DecodeSession:
             # step (draw=False), the rest is mh_sample_top_p_k
             if draw:
                 self.q_all[i].exponential_(1.0, generator=generator)
+            if self.row_params:  # the same kernel, row b on temp_rows[b], top_p_rows[b], top_k_rows[b] and its own two masks
+                ops.sample_top_p_k_rows(self.logits, self.first_mask, self.lo_tab, self.hi_tab, self.ev, i, self.q_all[i],
+                                        self.seq[:, i], self.V, self.temp_rows, self.top_p_rows, self.top_k_rows, self.ban,
+                                        out_b=self.samples_in, out_c=self.ev if i == 0 else None, first_span=self.first_span,
+                                        max_range=self.max_range[i], fill_rest=self.T - 1 if i == 0 else 0, fill_id=self.pad_id)
+                return
             ops.sample_top_p_k(self.logits, self.first_mask, self.lo_tab, self.hi_tab, self.ev, i, self.q_all[i], self.seq[:, i],
                                self.V, self.temp, self.top_p, self.top_k, out_b=self.samples_in,
                                out_c=self.ev if i == 0 else None, first_span=self.first_span, max_range=self.max_range[i],
@@ -323,11 +356,36 @@ class DecodeSession:
         self.hidden.copy_(y.view(B, S, spec.D)[:, -1])
         self.pos.fill_(S)
 
-    def set_limit(self, max_len: int) -> None:
-        """(ragged) the position rows are parked at, for this call: cache row max_len must exist"""
-        if max_len + 1 > self.cap:
-            raise ValueError(f"max_len {max_len} in a ragged session of capacity {self.cap} (max_len + 1 rows are needed)")
-        self.pos_limit.fill_(max_len)
+    def set_limit(self, max_len) -> None:
+        """(ragged) the position rows are parked at, for this call: cache row max_len must exist.  A row_params session also takes
+        a sequence of B limits, row b parked at max_len[b]."""
+        if isinstance(max_len, (int, np.integer)):
+            if max_len + 1 > self.cap:
+                raise ValueError(f"max_len {max_len} in a ragged session of capacity {self.cap} (max_len + 1 rows are needed)")
+            self.pos_limit.fill_(int(max_len))
+            return
+        lim = [int(n) for n in max_len]
+        if not self.row_params or len(lim) != self.B:
+            raise ValueError(f"set_limit: {len(lim)} limits for a session of {self.B} rows (row_params: {self.row_params})")
+        if max(lim) + 1 > self.cap:
+            raise ValueError(f"max_len {max(lim)} in a ragged session of capacity {self.cap} (max_len + 1 rows are needed)")
+        self.pos_limit.copy_(torch.tensor(lim, dtype=torch.int32))
+
+    def set_row_params(self, temp, top_p, top_k) -> None:
+        """(row_params) row b samples at temp[b], top_p[b], top_k[b] from now on: three B-element copies into the buffers the
+        captured sampler reads.  The values are the caller's to validate (model._row_params does); a top_k outside
+        [1, min(64, V)] is refused here as well, since this form has no sampler for it."""
+        if not self.row_params:
+            raise ValueError("set_row_params: not a row_params session")
+        vals = [list(np.asarray(x).reshape(-1).tolist()) for x in (temp, top_p, top_k)]
+        if any(len(v) != self.B for v in vals):
+            raise ValueError(f"set_row_params: {[len(v) for v in vals]} values for a session of {self.B} rows")
+        kmax = min(ops.SAMPLE_MAX_K, self.V)
+        if any(int(k) != k or not 1 <= k <= kmax for k in vals[2]):
+            raise ValueError(f"set_row_params: top_k {vals[2]} outside [1, {kmax}]")
+        self.temp_rows.copy_(torch.tensor(vals[0], dtype=torch.float32))
+        self.top_p_rows.copy_(torch.tensor(vals[1], dtype=torch.float32))
+        self.top_k_rows.copy_(torch.tensor(vals[2], dtype=torch.int32))
 
     def prefill_ragged(self, tokens: torch.Tensor, lengths) -> None:
         """tokens [M, T]: the B prompts laid end to end, prompt b of lengths[b] events.  One packed causal forward from empty

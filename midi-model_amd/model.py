@@ -511,20 +511,39 @@ class MIDIModel(nn.Module):
         bookkeeping per row, no extra sync; decode.py), the host drops what it samples.  The reference's break rule and its
         "every row sampled EOS" stop are evaluated over the live rows only, so with equal lengths this is the rule ``generate``
         runs; the noise is still ``[8, B, V]`` per event.  The call ends when no row is live or every live row sampled EOS, so a
-        row may come back shorter than ``max_len`` only through EOS.  The set of rows is fixed for the call; temperature, top-p,
-        top-k and ``max_len`` are the call's, not a row's.  ``ValueError`` before any launch: no prompts, an empty prompt, a
-        prompt of ``max_len`` events or more, ids outside the vocabulary, and what the mask options refuse in ``generate``.
+        row may come back shorter than ``max_len`` only through EOS.  The set of rows is fixed for the call.  ``ValueError`` before
+        any launch: no prompts, an empty prompt, a prompt of ``max_len`` events or more, ids outside the vocabulary, and what the
+        mask options refuse in ``generate``.
+
+        A value PER ROW: each of ``temp``, ``top_p``, ``top_k``, ``max_len``, ``ban_eos``, ``disable_patch_change`` and
+        ``disable_control_change`` is a scalar (every row's, as in ``generate``) or a sequence of B values, row b's at index b;
+        ``disable_channels`` is ``None``, a flat sequence of ints (every row's) or a sequence of B entries, each ``None`` or a
+        sequence of ints.  With scalars (and a flat channel list) alone the call runs the path, the session and the kernels it ran
+        before per-row values existed.  As soon as ONE argument is a sequence -- equal entries included -- the call runs on a
+        ``row_params`` session (decode.py): the values live in device buffers with one entry per row, the sampler is
+        ``mh_sample_top_p_k_rows`` (the uniform sampler's kernel, row b on its own values: same arithmetic, same id), and the
+        pooled session of a (B, capacity) serves every setting without a new K/V cache or a recapture.  Row b is then live while
+        L_b + t < max_len[b], the capacity follows max(max_len) + 1, and the break rule, the all-EOS stop, the ``[8, B, V]`` noise
+        per event and the generator's final state follow the rule above.  Further refusals of this form, all ``ValueError`` before
+        any launch: a sequence whose length is not B; a temperature that is not finite or not above 0; a NaN ``top_p``; a
+        ``top_k`` outside [1, min(64, V)] (the scalar path keeps its op-by-op sampler for larger k, this form has none); row b's
+        prompt holding ``max_len[b]`` events or more (the message names the row); per row, what the mask options refuse.
+        Out of scope: a generator per row (a row's draws depend on its batch mates: they share the ``[8, B, V]`` stream); per-row
+        values on ``generate`` / ``generate_stream`` / ``share_prompt``; admitting new rows into a running batch.
         The prompts are prefilled packed -- no padded event is computed; prompts of ONE length are prefilled by
         ``generate``'s uniform forward, so that for the same seeded generator the call returns exactly ``generate``'s ids.
         Speed against one ``generate`` call per distinct length: NOT MEASURED at this commit -- ``tools/bench_ragged.py`` is the
         vehicle and no MI355X run of it exists yet.  From launches alone: a decoded event costs about the same
         ~210 launches for 1 row as for 64, so B lengths in one batch should approach B times the useful events/s of B batches
         of one; the net graph gains two tiny launches (the position update) and nothing else."""
-        rows = self._ragged_prompts(prompts, max_len, None)
-        chans = self._check_mask_options(ban_eos, disable_patch_change, disable_control_change, disable_channels)
+        rp = self._row_params(prompts, max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change,
+                              disable_channels)
+        rows = self._ragged_prompts(prompts, max_len if rp is None else rp["max_len"], None)
+        chans = None if rp is not None else \
+            self._check_mask_options(ban_eos, disable_patch_change, disable_control_change, disable_channels)
         outs = [[r] for r in rows]
         for ev, live in self._generate_events_ragged(rows, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
-                                                     disable_control_change, chans):
+                                                     disable_control_change, chans, rp):
             for b in np.flatnonzero(live):
                 outs[b].append(ev[b][None])
         return [np.concatenate(o, axis=0) for o in outs]
@@ -534,13 +553,65 @@ class MIDIModel(nn.Module):
         """The serving form of ``generate_ragged``: a Python generator that yields, per event step, ``(events np.int64 (B, 8),
         live np.bool_ (B,))`` -- row b of ``events`` counts only where ``live[b]``.  Each prompt is cropped to its last 4096
         events first, as ``generate_stream`` crops.  The arguments are checked HERE, before the generator is handed out."""
-        rows = self._ragged_prompts(prompts, max_len, 4096)
-        chans = self._check_mask_options(ban_eos, disable_patch_change, disable_control_change, disable_channels)
+        rp = self._row_params(prompts, max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change,
+                              disable_channels)
+        rows = self._ragged_prompts(prompts, max_len if rp is None else rp["max_len"], 4096)
+        chans = None if rp is not None else \
+            self._check_mask_options(ban_eos, disable_patch_change, disable_control_change, disable_channels)
         return self._generate_events_ragged(rows, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
-                                            disable_control_change, chans)
+                                            disable_control_change, chans, rp)
 
-    def _ragged_prompts(self, prompts, max_len: int, crop) -> list:
-        """the prompts of generate_ragged as contiguous int64 arrays (L_b, 8): _prompt_tensor's range check and padding per row"""
+    @staticmethod
+    def _per_row(x) -> bool:
+        return isinstance(x, (list, tuple)) or (isinstance(x, (np.ndarray, torch.Tensor)) and x.ndim > 0)
+
+    def _row_params(self, prompts, max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change,
+                    disable_channels):
+        """The arguments of generate_ragged that take a value per row, checked on the host before any launch.  -> None when every
+        one of them is the call's (scalars; a flat list of channels): today's path.  Otherwise a dict of B-element lists -- scalars
+        repeated -- under the argument names, ``chans`` holding row b's sorted banned channels; every refusal is a ValueError."""
+        channels_per_row = self._per_row(disable_channels) and any(c is None or self._per_row(c) for c in disable_channels)
+        scalars = dict(max_len=max_len, temp=temp, top_p=top_p, top_k=top_k, ban_eos=ban_eos,
+                       disable_patch_change=disable_patch_change, disable_control_change=disable_control_change)
+        if not channels_per_row and not any(self._per_row(v) for v in scalars.values()):
+            return None
+        if prompts is None or len(prompts) == 0:
+            raise ValueError("generate_ragged: no prompts")
+        B = len(prompts)
+        rp = {}
+        for name, v in scalars.items():
+            v = list(v.tolist() if isinstance(v, (np.ndarray, torch.Tensor)) else v) if self._per_row(v) else [v] * B
+            if len(v) != B:
+                raise ValueError(f"generate_ragged: {name} holds {len(v)} values for {B} prompts")
+            rp[name] = v
+        chan_rows = list(disable_channels) if channels_per_row else [disable_channels] * B
+        if len(chan_rows) != B:
+            raise ValueError(f"generate_ragged: disable_channels holds {len(chan_rows)} entries for {B} prompts")
+        kmax = min(ops.SAMPLE_MAX_K, self.tokenizer.vocab_size)
+        rp["chans"] = []
+        for b in range(B):
+            t, p, k = rp["temp"][b], rp["top_p"][b], rp["top_k"][b]
+            if not (math.isfinite(t) and t > 0):
+                raise ValueError(f"generate_ragged: row {b}: temperature {t} is not a finite number above 0")
+            if math.isnan(p):
+                raise ValueError(f"generate_ragged: row {b}: top_p is NaN")
+            if int(k) != k or not 1 <= k <= kmax:
+                raise ValueError(f"generate_ragged: row {b}: top_k {k} outside [1, {kmax}] (per-row parameters run on the fused "
+                                 f"sampler alone)")
+            if int(rp["max_len"][b]) != rp["max_len"][b]:
+                raise ValueError(f"generate_ragged: row {b}: max_len {rp['max_len'][b]} is not an integer")
+            try:
+                rp["chans"].append(self._check_mask_options(rp["ban_eos"][b], rp["disable_patch_change"][b],
+                                                            rp["disable_control_change"][b], chan_rows[b]))
+            except ValueError as e:
+                raise ValueError(f"row {b}: {e}") from None
+        rp["max_len"] = [int(n) for n in rp["max_len"]]
+        rp["top_k"] = [int(k) for k in rp["top_k"]]
+        return rp
+
+    def _ragged_prompts(self, prompts, max_len, crop) -> list:
+        """the prompts of generate_ragged as contiguous int64 arrays (L_b, 8): _prompt_tensor's range check and padding per row.
+        ``max_len``: the call's, or a list with row b's"""
         self._require_gpu()
         tok = self.tokenizer
         T = tok.max_token_seq
@@ -558,25 +629,36 @@ class MIDIModel(nn.Module):
                 p = np.pad(p, ((0, 0), (0, T - p.shape[1])), mode="constant", constant_values=tok.pad_id)
             if crop is not None:
                 p = p[-crop:]
-            if p.shape[0] >= max_len:
-                raise ValueError(f"generate_ragged: prompt {b} has {p.shape[0]} events, max_len is {max_len}: nothing to generate")
+            limit = max_len[b] if isinstance(max_len, list) else max_len
+            if p.shape[0] >= limit:
+                raise ValueError(f"generate_ragged: prompt {b} has {p.shape[0]} events, max_len is {limit}: nothing to generate")
             rows.append(np.ascontiguousarray(p, dtype=np.int64))
         return rows
 
     def _generate_events_ragged(self, rows, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
-                                disable_control_change, chans):
+                                disable_control_change, chans, rp=None):
         """generator over (events (B, 8), live (B,)) of the checked prompts ``rows``; the session goes back to the pool when the
-        generator finishes or is closed.  The loop is _generate_events' with the live rows in place of all rows."""
+        generator finishes or is closed.  The loop is _generate_events' with the live rows in place of all rows.  ``rp`` (the
+        checked per-row arguments of _row_params, or None): the row_params session, row b live while L_b + t < max_len[b]."""
         lengths = np.array([r.shape[0] for r in rows], dtype=np.int64)
         B = len(rows)
         with torch.inference_mode():
-            ses = self._checkout_session(B, max_len + 1, float(temp), float(top_p), int(top_k), ragged=True)
+            if rp is not None:
+                max_len = np.array(rp["max_len"], dtype=np.int64)
+                # (1.0, 0.98, 1 fill a NEW session's buffers through its warm-up pass; set_row_params below overwrites them)
+                ses = self._checkout_session(B, int(max_len.max()) + 1, 1.0, 0.98, 1, ragged=True, row_params=True)
+            else:
+                ses = self._checkout_session(B, max_len + 1, float(temp), float(top_p), int(top_k), ragged=True)
         try:
             with torch.inference_mode():
-                self._set_masks(ses, ban_eos, disable_patch_change, disable_control_change, chans)
+                if rp is not None:
+                    self._set_masks_rows(ses, rp)
+                    ses.set_row_params(rp["temp"], rp["top_p"], rp["top_k"])
+                else:
+                    self._set_masks(ses, ban_eos, disable_patch_change, disable_control_change, chans)
                 ses.reset()
                 ses.begin(generator)
-                ses.set_limit(max_len)
+                ses.set_limit(max_len if rp is None else rp["max_len"])
                 packed = torch.from_numpy(np.concatenate(rows, axis=0)).to(self.device)
                 ses.prefill_ragged(packed, lengths.tolist())  # one packed causal forward; hidden[b] = prompt b's last position
             t = 0
@@ -669,6 +751,24 @@ class MIDIModel(nn.Module):
         for c in chans:
             ses.ban[tok.parameter_ids["channel"][c]] = 1
 
+    def _set_masks_rows(self, ses, rp) -> None:
+        """_set_masks per row of a row_params session: both [B, V] masks are built on the host and copied once"""
+        tok = self.tokenizer
+        B = len(rp["chans"])
+        first = self._grammar()[0].cpu()[None, :].repeat(B, 1)
+        ban = torch.zeros_like(first)
+        for b in range(B):
+            if rp["ban_eos"][b]:
+                first[b, tok.eos_id] = 0
+            if rp["disable_patch_change"][b]:
+                first[b, tok.event_ids["patch_change"]] = 0
+            if rp["disable_control_change"][b]:
+                first[b, tok.event_ids["control_change"]] = 0
+            for c in rp["chans"][b]:
+                ban[b, tok.parameter_ids["channel"][c]] = 1
+        ses.first_mask.copy_(first)
+        ses.ban.copy_(ban)
+
     def _generate_events(self, inp, batch_size, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
                          disable_control_change, disable_channels, shared: bool = False):
         """generator over the new events ((B, 8) int64 numpy each); the session is returned to the pool when the
@@ -713,10 +813,12 @@ class MIDIModel(nn.Module):
 
     # decode sessions: buffers + captured graphs, one per concurrent generate() call (decode.py)
     def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int, shared_need: int = 0,
-                          ragged: bool = False):
+                          ragged: bool = False, row_params: bool = False):
         """``shared_need`` > 0: a shared-prompt session whose prompt cache holds shared_need events (capacities by the same
         doubling rule from 256, so one captured session serves a range of prompt and suffix lengths).  ``ragged``: a session
-        with a position per row (generate_ragged), pooled like the others; not together with shared_need."""
+        with a position per row (generate_ragged), pooled like the others; not together with shared_need.  ``row_params``
+        (ragged only): the session that reads temperature, top-p, top-k, masks and limit per row from its own buffers; its key
+        holds none of them, so temp / top_p / top_k only fill the buffers of a session built here."""
         from .decode import DecodeSession
         cap = 256
         while cap < need:
@@ -726,7 +828,7 @@ class MIDIModel(nn.Module):
             scap = 256
             while scap < shared_need:
                 scap *= 2
-        key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged)
+        key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params)
         pool = self._sessions
         with pool.lock:
             found = None
@@ -739,7 +841,7 @@ class MIDIModel(nn.Module):
         if found is not None:
             found.refresh()  # weights may have been trained / merged since the session derived its folded copies
             return found
-        return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged)
+        return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params)
 
     def _return_session(self, ses) -> None:
         with self._sessions.lock:

@@ -607,9 +607,14 @@ _PACKED = ("SeqPlan", "attn_seq_plan", "rope_pos_", "attn_fwd_seqs", "attn_bwd_s
 _WIDE = ("gemm_skinny_wide", "skinny_wide_ok", "decode_wide_enabled")
 # ... and the grouped weight-gradient launch (ops_grouped.py; the emulation never takes it: it asks for device tensors)
 _GROUPED = ("wgrad_grouped", "wgrad_grouped_ok", "wgrad_grouped_operands_ok", "wgrad_grouped_enabled", "wgrad_grouped_launches")
+# ... and the fused sampler with a parameter set per row (ops_rows.py; stand-in in tests/emu_rowparams.py)
+_ROWS = ("sample_top_p_k_rows",)
 
 
 def __getattr__(name: str):
+    if name in _ROWS:
+        from . import ops_rows
+        return getattr(ops_rows, name)
     if name in _GROUPED:
         from . import ops_grouped
         return getattr(ops_grouped, name)

@@ -10,7 +10,13 @@ each first (it captures the sessions and warms the clocks), then (a) and (b) ALT
 is reported, with the spread).  The figure is USEFUL events/s: only events of live rows count, sum over rows of (max_len - L_b), the
 same number on both sides.  One JSON line on stdout (and in --out).
 
-usage: tools/bench_ragged.py [--B 64] [--max-len 1024] [--lmin 16] [--lmax 512] [--reps 3] [--out FILE]
+``--row-params`` measures something else: what a CHANGED sampling parameter costs the first call that carries it.  Per rep, a
+temperature no call has used yet goes (a) as a scalar -- generate_ragged has to build a session for it: a K/V cache and three
+captures -- and (b) as a list of B equal entries -- the pooled row_params session takes it as B-element copies -- alternating, whole
+calls timed as above, after one untimed call of each; (c) repeats (a)'s call, now on its pooled session: the call's cost without the
+build.  Use a short --max-len (the default becomes lmax + 16) so that the calls are not dominated by decoding.
+
+usage: tools/bench_ragged.py [--B 64] [--max-len 1024] [--lmin 16] [--lmax 512] [--reps 3] [--out FILE] [--row-params]
 
 Result: NOT MEASURED at this commit unless profiles/ holds a line of this tool (DESIGN 7.4 quotes it when it does)."""
 import argparse
@@ -46,12 +52,14 @@ def timed(fn):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=64)
-    ap.add_argument("--max-len", type=int, default=1024)
+    ap.add_argument("--max-len", type=int, default=0, help="default 1024; with --row-params lmax + 16")
     ap.add_argument("--lmin", type=int, default=16)
     ap.add_argument("--lmax", type=int, default=512)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default="")
+    ap.add_argument("--row-params", action="store_true", help="first-call cost of a changed parameter: new session vs row_params")
     a = ap.parse_args()
+    a.max_len = a.max_len or (a.lmax + 16 if a.row_params else 1024)
     if not torch.cuda.is_available():
         raise SystemExit("bench_ragged: needs a GPU (no timing is taken without one)")
     torch.manual_seed(0)
@@ -63,6 +71,36 @@ def main():
     groups = {}
     for b, L in enumerate(lengths):
         groups.setdefault(L, []).append(b)
+
+    def emit(res):
+        line = json.dumps(res)
+        print(line, flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+
+    if a.row_params:
+        def call(temp):
+            out = model.generate_ragged(prompts, max_len=a.max_len, temp=temp, ban_eos=True,
+                                        generator=torch.Generator(device="cuda").manual_seed(1))
+            assert sum(len(r) - L for r, L in zip(out, lengths)) == useful
+
+        call(1.0), call([1.0] * a.B)   # untimed: one session of each form captured and pooled, clocks warm
+        t = {"new_scalar_setting": [], "new_row_params_setting": [], "scalar_setting_again": []}
+        for r in range(a.reps):
+            temp = 1.0 + 0.01 * (r + 1)
+            t["new_scalar_setting"].append(timed(lambda: call(temp)))
+            t["new_row_params_setting"].append(timed(lambda: call([temp] * a.B)))
+            t["scalar_setting_again"].append(timed(lambda: call(temp)))
+        res = {"tool": "bench_ragged --row-params", "device": torch.cuda.get_device_name(0), "model": "tv2o-medium", "dtype": "bf16",
+               "B": a.B, "max_len": a.max_len, "lengths": [a.lmin, a.lmax], "useful_events": useful, "reps": a.reps}
+        for k, v in t.items():
+            res[k] = {"seconds": [round(x, 4) for x in v], "median_seconds": round(statistics.median(v), 4)}
+        res["saved_seconds_per_changed_setting"] = round(statistics.median(t["new_scalar_setting"])
+                                                         - statistics.median(t["new_row_params_setting"]), 4)
+        emit(res)
+        return
 
     def ragged():
         out = model.generate_ragged(prompts, max_len=a.max_len, ban_eos=True, generator=torch.Generator(device="cuda").manual_seed(1))
@@ -89,12 +127,7 @@ def main():
                   "median_events_per_s": round(useful / statistics.median(v), 1),
                   "spread": round((max(v) - min(v)) / statistics.median(v), 4)}
     res["ragged_over_serial"] = round(statistics.median(t["serial"]) / statistics.median(t["ragged"]), 3)
-    line = json.dumps(res)
-    print(line, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    emit(res)
 
 
 if __name__ == "__main__":

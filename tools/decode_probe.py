@@ -185,9 +185,47 @@ def section_3(model, n_events=192):
     ops.set_option("skinny_mb", 0)
 
 
+def section_4(B=64, V=3406, rounds=3):
+    print(f"== 4. fused sampler, uniform (mh_sample_top_p_k) against per-row (mh_sample_top_p_k_rows): us per launch, 48 launches in a "
+          f"replayed graph, B={B}, bf16, runs alternating ==")
+    g = torch.Generator().manual_seed(0)
+    logits = (3.0 * torch.randn((B, V + (-V) % 8), generator=g)).to(dev, bf)
+    q = torch.empty((B, V)).exponential_(1.0, generator=g).to(dev)
+    out = torch.zeros((B,), dtype=torch.long, device=dev)
+    ev = torch.arange(B, device=dev)
+    fm, ban = torch.zeros(V, dtype=torch.uint8, device=dev), torch.zeros(V, dtype=torch.uint8, device=dev)
+    fm_rows, ban_rows = fm[None].repeat(B, 1), ban[None].repeat(B, 1)
+    temp, top_p = torch.full((B,), 1.0, device=dev), torch.full((B,), 0.98, device=dev)
+    top_k = torch.full((B,), 20, dtype=torch.int32, device=dev)
+    for span, inst in ((128, "TMAX 2"), (512, "TMAX 8"), (2048, "TMAX 32")):
+        lo = (torch.arange(B, dtype=torch.int32) * 7 + 1) % (V - span)
+        lo_tab = torch.stack([torch.zeros_like(lo), lo], 1).contiguous().to(dev)
+        hi_tab = torch.stack([torch.zeros_like(lo), lo + span], 1).contiguous().to(dev)
+
+        def uniform():
+            for _ in range(48):
+                ops.sample_top_p_k(logits, fm, lo_tab, hi_tab, ev, 1, q, out, V, 1.0, 0.98, 20, max_range=span, ban_mask=ban)
+
+        def rows(first=fm, banned=ban):
+            for _ in range(48):
+                ops.sample_top_p_k_rows(logits, first, lo_tab, hi_tab, ev, 1, q, out, V, temp, top_p, top_k, banned, max_range=span)
+
+        def rows_bv():
+            rows(fm_rows, ban_rows)
+        t = {"uniform": [], "rows": [], "rows, [B, V] masks": []}
+        for _ in range(rounds):
+            for name, body in (("uniform", uniform), ("rows", rows), ("rows, [B, V] masks", rows_bv)):
+                t[name].append(1e3 * graph_time(body) / 48)
+        print(f"{inst} (ranges of {span} ids): " + ";  ".join(f"{k} " + " ".join(f"{x:.2f}" for x in v) for k, v in t.items()))
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     which = sys.argv[1:] or ["1", "2", "3"]
+    if "4" in which:
+        section_4()
+        if which == ["4"]:
+            sys.exit(0)
     if "1" in which:
         section_1()
     if "1b" in which:
