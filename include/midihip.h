@@ -478,6 +478,13 @@ int mh_kv_store_prefill(const void* qkv, void* kcache, void* vcache, int64_t B, 
  * Lmax instead of writing it.                                                                                               */
 int mh_kv_store_seqs(const void* qkv, const int32_t* seq_start, void* kcache, void* vcache, int64_t n, int64_t M, int H, int hd,
                      int64_t Lmax, int dtype, void* stream);
+/* mh_kv_store_seqs into CHOSEN sequences of a cache that is already in use (DecodeSession.admit): rows device int32 [n], sequence
+ * s goes to cache sequence rows[s] of k,v [B,H,Lmax,hd] -- rows [0, L_s) of it -- and no other cache element is written.  n <= B
+ * (the host refuses n > B and M > n * Lmax); the row ids must be distinct and inside [0, B): the caller
+ * (midi_model_amd.ops.kv_store_seqs_rows) checks its host copy of them and of the lengths, and the kernel drops a sequence whose
+ * row id is outside [0, B), and a row at or past Lmax, instead of writing it.                                                */
+int mh_kv_store_seqs_rows(const void* qkv, const int32_t* seq_start, const int32_t* rows, void* kcache, void* vcache, int64_t n,
+                          int64_t B, int64_t M, int H, int hd, int64_t Lmax, int dtype, void* stream);
 
 /* ---- grammar-masked softmax for the sampler (midi_model.py:202-223) -----------------------------------------
  * probs[b,:] = softmax(logits[b,:]/temp) * mask_b, mask_b = ids in [lo[b],hi[b]) or, when lo[b] < 0, the

@@ -593,10 +593,12 @@ extern "C" int mh_kv_store_prefill(const void* qkv, void* kcache, void* vcache, 
 // Packed prefill (generate_ragged): row m of qkv [M, 3 H hd] belongs to the sequence s with seq_start[s] <= m < seq_start[s + 1]
 // and goes to cache row m - seq_start[s] of (s, h).  One lane per 16 bytes of a K row and of a V row; the sequence is found by
 // bisection of the (L2-resident, n + 1 entries) table.  A row at or past Lmax is dropped, never written.
-template <typename T>
+// ROWS (DecodeSession.admit): sequence s goes to cache sequence rows[s] (device int32 [n]) of a cache of B sequences instead of
+// cache sequence s; a sequence whose rows[s] is outside [0, B) is dropped as well.  One more (L2-resident) load per lane.
+template <typename T, bool ROWS = false>
 __global__ __launch_bounds__(256) void kv_store_seqs_kernel(const T* __restrict__ qkv, const int32_t* __restrict__ seq_start,
                                                             T* __restrict__ kc, T* __restrict__ vc, int n, int64_t M, int H,
-                                                            int hd, int64_t Lmax) {
+                                                            int hd, int64_t Lmax, const int32_t* __restrict__ rows, int B) {
   constexpr int N = Pack<T>::N;
   const int cph = hd / N;
   const int64_t total = M * H * cph;
@@ -614,8 +616,13 @@ __global__ __launch_bounds__(256) void kv_store_seqs_kernel(const T* __restrict_
   }
   const int64_t row = m - seq_start[lo];
   if (row < 0 || row >= Lmax) return;
+  int seq = lo;
+  if constexpr (ROWS) {
+    seq = rows[lo];
+    if (seq < 0 || seq >= B) return;
+  }
   const T* src = qkv + m * 3 * D + (int64_t)h * hd + c * N;
-  const int64_t dst = (((int64_t)lo * H + h) * Lmax + row) * hd + c * N;
+  const int64_t dst = (((int64_t)seq * H + h) * Lmax + row) * hd + c * N;
   st16(kc + dst, ld16(src + D));
   st16(vc + dst, ld16(src + 2 * D));
 }
@@ -632,8 +639,29 @@ extern "C" int mh_kv_store_seqs(const void* qkv, const int32_t* seq_start, void*
   const int64_t total = M * H * (hd / (dtype == MH_BF16 ? 8 : 4));
   const int64_t g = (total + 255) / 256;
   MH_REQUIRE(g < (1ll << 31), "kv_store_seqs: %ld workgroups", (long)g);
-  DISPATCH_T(dtype, (kv_store_seqs_kernel<T><<<(unsigned)g, 256, 0, (hipStream_t)stream>>>((const T*)qkv, seq_start, (T*)kcache,
-                                                                                           (T*)vcache, (int)n, M, H, hd, Lmax)));
+  DISPATCH_T(dtype, (kv_store_seqs_kernel<T><<<(unsigned)g, 256, 0, (hipStream_t)stream>>>(
+                        (const T*)qkv, seq_start, (T*)kcache, (T*)vcache, (int)n, M, H, hd, Lmax, nullptr, 0)));
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// (rows lives in device memory too: the host refuses n > B -- n distinct rows cannot fit B -- and the kernel drops a sequence whose
+//  row id is outside [0, B); ops.kv_store_seqs_rows checks the host copy of the ids, in range and distinct, before the call)
+extern "C" int mh_kv_store_seqs_rows(const void* qkv, const int32_t* seq_start, const int32_t* rows, void* kcache, void* vcache,
+                                     int64_t n, int64_t B, int64_t M, int H, int hd, int64_t Lmax, int dtype, void* stream) {
+  MH_REQUIRE(qkv != nullptr && seq_start != nullptr && kcache != nullptr && vcache != nullptr, "kv_store_seqs_rows: null buffer");
+  MH_REQUIRE(rows != nullptr, "kv_store_seqs_rows: rows is NULL (one device int32 cache row per sequence)");
+  MH_REQUIRE(dtype == MH_BF16 || dtype == MH_F32, "kv_store_seqs_rows: bad dtype %d", dtype);
+  MH_REQUIRE(n > 0 && B > 0 && B < (1 << 30) && M >= n && M < (1ll << 31) && H > 0 && hd > 0 && hd % 8 == 0 && Lmax > 0,
+             "kv_store_seqs_rows: bad args n=%ld B=%ld M=%ld H=%d hd=%d Lmax=%ld", (long)n, (long)B, (long)M, H, hd, (long)Lmax);
+  MH_REQUIRE(n <= B, "kv_store_seqs_rows: %ld sequences for a cache of %ld", (long)n, (long)B);
+  MH_REQUIRE(M <= n * Lmax, "kv_store_seqs_rows: %ld rows in %ld sequences: a length exceeds Lmax=%ld", (long)M, (long)n,
+             (long)Lmax);
+  const int64_t total = M * H * (hd / (dtype == MH_BF16 ? 8 : 4));
+  const int64_t g = (total + 255) / 256;
+  MH_REQUIRE(g < (1ll << 31), "kv_store_seqs_rows: %ld workgroups", (long)g);
+  DISPATCH_T(dtype, (kv_store_seqs_kernel<T, true><<<(unsigned)g, 256, 0, (hipStream_t)stream>>>(
+                        (const T*)qkv, seq_start, (T*)kcache, (T*)vcache, (int)n, M, H, hd, Lmax, rows, (int)B)));
   MH_LAUNCH_CHECK();
   return MH_OK;
 }

@@ -43,6 +43,21 @@ live in session buffers with one entry per row -- ``temp_rows``, ``top_p_rows``,
 addresses, not values, and the pool key holds no sampling parameter: one session serves every setting of its (B, capacity), and
 a new setting is B-element copies (set_row_params, set_limit) instead of a new K/V cache and three captures.  The form has no
 op-by-op sampler behind it: it needs the fused kernel (grammar spans of at most 2048 ids, top_k <= 64).
+
+``admit`` / ``release`` (row_params sessions; pool.DecodePool drives them): rows of a RUNNING batch change hands between two
+events.  ``admit(rows, ...)`` runs one packed forward over the new prompts alone, stores their K/V into cache rows ``rows``
+(mh_kv_store_seqs_rows) and overwrites those rows of ``hidden``, ``pos``, ``pos_limit``, the three sampler arrays and the two masks;
+``release(rows)`` sets pos = pos_limit = 0 there, so that a free row attends to one key.  STREAM ORDER is the correctness argument:
+  1. the net step over the event just sampled runs for ALL rows first -- with ``then_net`` it is already queued behind the token
+     steps, otherwise the caller queues it before it admits; it reads and advances ``pos`` and writes ``hidden`` of every row;
+  2. the admission follows ON THE SAME STREAM and overwrites ``hidden``, ``pos`` and cache rows [0, L) of the admitted rows, so
+     what step 1 left there (the continuation of a request that has finished, or of nothing) is gone before anything reads it;
+  3. the next token steps, on the same stream again, sample every row from ``hidden``, the admitted rows from their prompts' last
+     positions.
+Stale K/V at cache rows >= L of a reused row is never read: attention reads rows [0, pos] and every one of them has been written
+since the admission -- [0, L) by the prefill, row p by the net step that stood at p.  The noise graph runs on its own stream and
+touches ``q_all`` alone, the copy stream reads ``seq`` alone; an admission writes neither.  No graph is recaptured and no graph
+body changes: every buffer named above sits at the address the captures hold.
 """
 from __future__ import annotations
 
@@ -147,6 +162,7 @@ class DecodeSession:
         self.use_graphs = graphs_enabled(dev)
         self.gen = torch.Generator(device=dev) if self.use_graphs else None  # the generator the captured sampler draws from
         self._user_gen = None
+        self._admit_stage = None   # the pinned host block of the last admission (admit)
         self._pool = None
         self._off = 0          # philox offset of the next draw the reference loop would make
         self._draw_inc = 0     # philox offset consumed by one [B, V] exponential_ call
@@ -419,6 +435,92 @@ class DecodeSession:
         y = engine.stack_prefill_seqs(spec, m._W["net"], e, plan, self.rope1, self.kv1, folded=self.fold1)
         self.hidden.copy_(y.index_select(0, plan.seq_start[1:].long() - 1))
         self.pos.copy_(plan.seq_start[1:] - plan.seq_start[:-1])
+
+    def admit(self, rows, tokens: torch.Tensor, lengths, limits, temp, top_p, top_k, first_masks, bans) -> None:
+        """(row_params) n new requests into rows ``rows`` of the running batch, between two events (the header has the stream-order
+        argument).  tokens [M, T]: the n prompts laid end to end, prompt s of lengths[s] events; limits[s]: the position row
+        rows[s] is parked at (its max_len); temp / top_p / top_k: n values; first_masks / bans: uint8 [n, V] (host).  ONE packed
+        forward over the admitted prompts alone -- always the packed form, also for one prompt or equal lengths, so that a
+        request's prefill depends on its admission group through that forward's own shape dispatch and through nothing else --
+        K/V into cache rows ``rows``, hidden[rows] = each prompt's last position, pos[rows] = lengths, and pos_limit, the sampler
+        arrays and both masks of those rows overwritten.  The per-row values travel in ONE pinned host block and are scattered by
+        eight index_copy_ calls (and one index_select for the last positions): no kernel of their own.  Everything is checked
+        on the host first; ``ValueError`` before any launch."""
+        if not (self.ragged and self.row_params):
+            raise ValueError("DecodeSession.admit: rows are admitted into a ragged=True, row_params=True session only")
+        from .ops_pool import check_rows
+        m = self.model
+        spec = m._specs["net"]
+        lengths, limits = [int(n) for n in lengths], [int(n) for n in limits]
+        n, V = len(lengths), self.V
+        ids = check_rows(rows, n, self.B)
+        vals = [list(np.asarray(x).reshape(-1).tolist()) for x in (temp, top_p, top_k)]
+        first_masks, bans = torch.as_tensor(first_masks), torch.as_tensor(bans)
+        M, T = tokens.shape
+        if n < 1 or min(lengths) < 1 or sum(lengths) != M or T != self.T or len(limits) != n or any(len(v) != n for v in vals):
+            raise ValueError(f"admit: {n} lengths summing to {sum(lengths)} for {M} rows of {T} tokens, {len(limits)} limits, "
+                             f"{[len(v) for v in vals]} sampler values")
+        if any(L > lim or lim + 1 > self.cap for L, lim in zip(lengths, limits)):
+            raise ValueError(f"admit: prompts of {lengths} events, limits {limits}, in a session of capacity {self.cap} (a prompt "
+                             f"may not exceed its limit, and limit + 1 rows are needed)")
+        kmax = min(ops.SAMPLE_MAX_K, V)
+        if any(int(k) != k or not 1 <= k <= kmax for k in vals[2]):
+            raise ValueError(f"admit: top_k {vals[2]} outside [1, {kmax}]")
+        for name, t in (("first_masks", first_masks), ("bans", bans)):
+            if t.dtype != torch.uint8 or t.shape != (n, V) or t.device.type != "cpu":
+                raise ValueError(f"admit: {name} must be a host uint8 tensor [{n}, {V}]: {t.dtype} {tuple(t.shape)} on {t.device}")
+        # ---- the one host block: [idx i64 | last i64 | rows i32 | lengths i32 | limits i32 | top_k i32 | temp f32 | top_p f32 |
+        #      first u8 | ban u8], every section on a multiple of 16 bytes
+        sections = [(np.int64, ids), (np.int64, np.cumsum(lengths) - 1), (np.int32, ids), (np.int32, lengths), (np.int32, limits),
+                    (np.int32, vals[2]), (np.float32, vals[0]), (np.float32, vals[1]),
+                    (np.uint8, first_masks.numpy().reshape(-1)), (np.uint8, bans.numpy().reshape(-1))]
+        parts, offs, at = [], [], 0
+        for ty, v in sections:
+            a = np.ascontiguousarray(np.asarray(v, dtype=ty)).view(np.uint8)
+            parts.append(a)
+            offs.append((at, a.size))
+            at += (a.size + 15) // 16 * 16
+        host = np.zeros(at, dtype=np.uint8)
+        for a, (o, sz) in zip(parts, offs):
+            host[o:o + sz] = a
+        dev = m.device
+        block = torch.from_numpy(host)
+        if dev.type == "cuda":  # pinned staging, non-blocking (as SeqPlan.upload); kept alive until the next admission
+            self._admit_stage = block.pin_memory()
+            block = self._admit_stage.to(dev, non_blocking=True)
+        tys = (torch.int64, torch.int64, torch.int32, torch.int32, torch.int32, torch.int32, torch.float32, torch.float32,
+               torch.uint8, torch.uint8)
+        idx, last, rows_dev, len_dev, lim_dev, k_dev, t_dev, p_dev, first_dev, ban_dev = \
+            (block[o:o + sz].view(ty) for ty, (o, sz) in zip(tys, offs))
+        # ---- one packed forward over the admitted prompts alone, K/V into the chosen cache rows
+        plan = ops.attn_seq_plan(lengths, spec.H).upload(dev)
+        e = torch.empty((M, spec.D), dtype=m.dtype, device=dev)
+        ops.embed_sum_fwd(tokens.to(dev).contiguous(), m._W["net"].embed, e)
+        y = engine.stack_prefill_seqs(spec, m._W["net"], e, plan, self.rope1, self.kv1, folded=self.fold1, rows=ids,
+                                      rows_dev=rows_dev)
+        # ---- the rows' state
+        self.hidden.index_copy_(0, idx, y.index_select(0, last))
+        self.pos.index_copy_(0, idx, len_dev)
+        self.pos_limit.index_copy_(0, idx, lim_dev)
+        self.temp_rows.index_copy_(0, idx, t_dev)
+        self.top_p_rows.index_copy_(0, idx, p_dev)
+        self.top_k_rows.index_copy_(0, idx, k_dev)
+        self.first_mask.index_copy_(0, idx, first_dev.view(n, V))
+        self.ban.index_copy_(0, idx, ban_dev.view(n, V))
+
+    def release(self, rows) -> None:
+        """(row_params) rows whose requests have finished: pos = pos_limit = 0 there.  A free row is still embedded, attended and
+        sampled with the rest of the batch, but it now attends to ONE key (the row it overwrites at position 0) instead of
+        dragging a finished request's whole cache through the attention kernel; what it samples is the caller's to drop."""
+        if not (self.ragged and self.row_params):
+            raise ValueError("DecodeSession.release: rows are released on a ragged=True, row_params=True session only")
+        from .ops_pool import check_rows
+        ids = check_rows(rows, len(rows), self.B)
+        if not ids:
+            return
+        idx = torch.tensor(ids, dtype=torch.int64).to(self.model.device)
+        self.pos.index_fill_(0, idx, 0)
+        self.pos_limit.index_fill_(0, idx, 0)
 
     def begin(self, generator) -> None:
         """take over the caller's random stream (None = the device's default generator)"""

@@ -636,17 +636,30 @@ def stack_prefill(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, 
     return y
 
 
-def stack_prefill_seqs(spec: StackSpec, W: StackTensors, x: torch.Tensor, plan, rope: RopeTable, kv: KVState, folded=None):
+def stack_prefill_seqs(spec: StackSpec, W: StackTensors, x: torch.Tensor, plan, rope: RopeTable, kv: KVState, folded=None,
+                       rows=None, rows_dev=None):
     """stack_prefill for prompts of DIFFERENT lengths (generate_ragged): ``x`` [M, D] holds plan.n sequences laid end to end
     (``plan`` = an uploaded ops.SeqPlan), sequence s fills rows [0, L_s) of its own cache -- one packed forward, then one
     kv_store_seqs launch per layer.  kv.len is left alone: the rows stand at different positions, which the caller keeps
-    (a ragged decode session: ``pos`` on the device)."""
-    assert kv.B == plan.n and plan.M == x.shape[0]
-    kv.reserve(plan.max_len)
+    (a ragged decode session: ``pos`` on the device).
+    ``rows`` (DecodeSession.admit; a sequence of plan.n distinct ints inside [0, kv.B), ``rows_dev`` its int32 device copy):
+    sequence s fills rows [0, L_s) of cache sequence rows[s] of a cache that is IN USE -- kv.B may exceed plan.n, the cache is not
+    grown (a captured graph holds its address), and the other sequences are not touched: one kv_store_seqs_rows launch per layer."""
+    assert plan.M == x.shape[0]
+    if rows is None:
+        assert kv.B == plan.n
+        kv.reserve(plan.max_len)
+    else:
+        assert plan.n <= kv.B
+        if plan.max_len > kv.cap:
+            raise ValueError(f"stack_prefill_seqs: a sequence of {plan.max_len} rows into a live cache of {kv.cap}")
     qkvs: list = []
     y, _ = stack_forward(spec, W, x, 1, plan.M, rope, save=False, kv_out=qkvs, folded=folded, seqs=plan)
     for li, qkv in enumerate(qkvs):
-        ops.kv_store_seqs(qkv, plan, kv.k[li], kv.v[li], spec.H, spec.hd, kv.cap)
+        if rows is None:
+            ops.kv_store_seqs(qkv, plan, kv.k[li], kv.v[li], spec.H, spec.hd, kv.cap)
+        else:
+            ops.kv_store_seqs_rows(qkv, plan, rows, kv.k[li], kv.v[li], spec.H, spec.hd, kv.cap, rows_dev=rows_dev)
     return y
 
 

@@ -511,7 +511,8 @@ class MIDIModel(nn.Module):
         bookkeeping per row, no extra sync; decode.py), the host drops what it samples.  The reference's break rule and its
         "every row sampled EOS" stop are evaluated over the live rows only, so with equal lengths this is the rule ``generate``
         runs; the noise is still ``[8, B, V]`` per event.  The call ends when no row is live or every live row sampled EOS, so a
-        row may come back shorter than ``max_len`` only through EOS.  The set of rows is fixed for the call.  ``ValueError`` before
+        row may come back shorter than ``max_len`` only through EOS.  The set of rows is fixed for the call (``decode_pool`` admits
+        and releases rows while the batch runs).  ``ValueError`` before
         any launch: no prompts, an empty prompt, a prompt of ``max_len`` events or more, ids outside the vocabulary, and what the
         mask options refuse in ``generate``.
 
@@ -529,7 +530,8 @@ class MIDIModel(nn.Module):
         ``top_k`` outside [1, min(64, V)] (the scalar path keeps its op-by-op sampler for larger k, this form has none); row b's
         prompt holding ``max_len[b]`` events or more (the message names the row); per row, what the mask options refuse.
         Out of scope: a generator per row (a row's draws depend on its batch mates: they share the ``[8, B, V]`` stream); per-row
-        values on ``generate`` / ``generate_stream`` / ``share_prompt``; admitting new rows into a running batch.
+        values on ``generate`` / ``generate_stream`` / ``share_prompt``.  Admitting new rows into a running batch is not this call's
+        job: ``decode_pool`` / ``generate_pool`` do that (pool.py).
         The prompts are prefilled packed -- no padded event is computed; prompts of ONE length are prefilled by
         ``generate``'s uniform forward, so that for the same seeded generator the call returns exactly ``generate``'s ids.
         Speed against one ``generate`` call per distinct length: NOT MEASURED at this commit -- ``tools/bench_ragged.py`` is the
@@ -751,8 +753,8 @@ class MIDIModel(nn.Module):
         for c in chans:
             ses.ban[tok.parameter_ids["channel"][c]] = 1
 
-    def _set_masks_rows(self, ses, rp) -> None:
-        """_set_masks per row of a row_params session: both [B, V] masks are built on the host and copied once"""
+    def _mask_rows(self, rp):
+        """the checked per-row mask options as two host uint8 tensors [B, V]: (first-token mask, banned ids)"""
         tok = self.tokenizer
         B = len(rp["chans"])
         first = self._grammar()[0].cpu()[None, :].repeat(B, 1)
@@ -766,8 +768,53 @@ class MIDIModel(nn.Module):
                 first[b, tok.event_ids["control_change"]] = 0
             for c in rp["chans"][b]:
                 ban[b, tok.parameter_ids["channel"][c]] = 1
+        return first, ban
+
+    def _set_masks_rows(self, ses, rp) -> None:
+        """_set_masks per row of a row_params session: both [B, V] masks are built on the host and copied once"""
+        first, ban = self._mask_rows(rp)
         ses.first_mask.copy_(first)
         ses.ban.copy_(ban)
+
+    def _check_request(self, prompt, max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change,
+                       disable_channels, crop=4096):
+        """ONE request of a decode pool, checked as generate_ragged checks a row with values of its own (_row_params,
+        _check_mask_options, _ragged_prompts: their code, their ValueErrors, before any launch) -> (prompt (L, 8) int64 cropped to
+        its last ``crop`` events, the one-row dict of _row_params)"""
+        if any(self._per_row(v) for v in (max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change)):
+            raise ValueError("a request takes one value per option: a scalar max_len, temp, top_p, top_k and mask option")
+        if disable_channels is not None and (not self._per_row(disable_channels) or any(
+                c is None or self._per_row(c) for c in disable_channels)):
+            raise ValueError("a request's disable_channels is None or a flat sequence of channel numbers")
+        rp = self._row_params([prompt], [max_len], [temp], [top_p], [top_k], [ban_eos], [disable_patch_change],
+                              [disable_control_change], [disable_channels])
+        return self._ragged_prompts([prompt], rp["max_len"], crop)[0], rp
+
+    def decode_pool(self, rows: int, capacity: int, generator=None):
+        """(ours) a ``pool.DecodePool`` on this model: ``rows`` decode rows that requests are admitted into and released from
+        while the batch runs (continuous batching).  ``capacity``: cache rows per decode row; a request needs
+        max_len + 1 <= capacity (the session's own capacity is rounded up as every session's is, 256 x 2^k).  The pool takes one
+        pooled ``row_params`` session at its first admission and holds it until ``close()`` (it is a context manager); it draws
+        from ``generator`` as ``generate_ragged`` does.  Nothing is launched here."""
+        from .pool import DecodePool
+        return DecodePool(self, rows, capacity, generator)
+
+    def generate_pool(self, requests, rows: int, capacity: Optional[int] = None, generator=None) -> list:
+        """(ours) ``requests``: a list of dicts, each the keyword arguments of ``DecodePool.submit`` (``prompt`` and any of max_len,
+        temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change, disable_channels).  They are submitted in order
+        to one pool of ``rows`` rows and stepped until all are done: a request waits only until a row is free, and a row that
+        finishes is handed to the next request at once.  -> a list of ``np.ndarray (<= max_len, 8) int64``, request i's at index
+        i, its prompt in front.  ``capacity`` defaults to the largest max_len + 1."""
+        requests = list(requests)
+        if not requests:
+            return []
+        if capacity is None:
+            capacity = max(int(r.get("max_len", 512)) for r in requests) + 1
+        with self.decode_pool(rows, capacity, generator) as pool:
+            ids = [pool.submit(**r) for r in requests]
+            while pool.pending():
+                pool.step()
+            return [pool.result(i) for i in ids]
 
     def _generate_events(self, inp, batch_size, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
                          disable_control_change, disable_channels, shared: bool = False):

@@ -609,9 +609,14 @@ _WIDE = ("gemm_skinny_wide", "skinny_wide_ok", "decode_wide_enabled")
 _GROUPED = ("wgrad_grouped", "wgrad_grouped_ok", "wgrad_grouped_operands_ok", "wgrad_grouped_enabled", "wgrad_grouped_launches")
 # ... and the fused sampler with a parameter set per row (ops_rows.py; stand-in in tests/emu_rowparams.py)
 _ROWS = ("sample_top_p_k_rows",)
+# ... and the packed K/V store into chosen rows of a live cache (ops_pool.py; stand-in in tests/emu_pool.py)
+_POOL = ("kv_store_seqs_rows",)
 
 
 def __getattr__(name: str):
+    if name in _POOL:
+        from . import ops_pool
+        return getattr(ops_pool, name)
     if name in _ROWS:
         from . import ops_rows
         return getattr(ops_rows, name)
