@@ -524,6 +524,28 @@ int mh_sample_top_p_k_rows(const void* logits, int64_t ldl, const uint8_t* first
                            int pos, const float* q, int64_t* out, int64_t out_stride, int64_t* out_b, int64_t* out_c,
                            int64_t B, int V, const float* temp, const float* top_p, const int32_t* top_k, int fill_rest,
                            int64_t fill_id, int dtype, void* stream);
+/* The seeded form of mh_sample_top_p_k_rows (a decode pool with a seed per request): the argument list of the per-row form with `q`
+ * replaced by `seed` (uint64 [B]) and `ctr` (int32 [B]), DEVICE arrays, required, read on the device like temp[b] -- one scalar load
+ * each per workgroup -- so a captured graph serves every seed.  Row b's variate for rank j (the j-th largest probability) at token
+ * position `pos` is COMPUTED by the lanes that need one instead of loaded:
+ *     x = word 0 of Philox4x32-10(counter = (uint32 ctr[b], uint32 pos, uint32 j, 0), key = (low, high 32 bits of seed[b]))
+ *     u = (2 (x >> 9) + 1) * 2^-24        exact in fp32, in [2^-24, 1 - 2^-24]
+ *     q = -logf(u)                        the accurate logf: never 0, infinite or NaN
+ * (Random123's constants and round function).  ctr[b] is the index of the event being sampled in the request's result -- prompt
+ * events plus events generated so far -- so a row's noise is a function of (seed, event, position, rank) and of nothing its batch
+ * mates do, its row number included.  Past q the kernel is the per-row form's: given a q [B, V] whose first 64 columns are what
+ * mh_sample_noise_seeded writes, mh_sample_top_p_k_rows returns the same ids.  Same argument checks; a NULL seed or ctr is
+ * refused by name.                                                                                                              */
+int mh_sample_top_p_k_seeded(const void* logits, int64_t ldl, const uint8_t* first_mask, int64_t first_stride,
+                             const uint8_t* ban_mask, int64_t ban_stride, int first_lo, int first_hi,
+                             const int32_t* lo_tab, const int32_t* hi_tab, int tab_stride, int max_range, const int64_t* ev,
+                             int pos, const uint64_t* seed, const int32_t* ctr, int64_t* out, int64_t out_stride, int64_t* out_b,
+                             int64_t* out_c, int64_t B, int V, const float* temp, const float* top_p, const int32_t* top_k,
+                             int fill_rest, int64_t fill_id, int dtype, void* stream);
+/* The generator of the seeded form on its own: bits[b, j] = x and q[b, j] = the variate above for the 64 ranks j of every row b
+ * at token position `pos` (uint32 / float [B, 64], device), through the device function the sampler calls.  A host caller gets a
+ * request's variates from it; the tests read the generator through it.                                                         */
+int mh_sample_noise_seeded(const uint64_t* seed, const int32_t* ctr, int pos, int64_t B, uint32_t* bits, float* q, void* stream);
 
 /* ---- the data-parallel gradient exchange on RCCL (reference: DDP under Lightning, train.py:461-474) -----------------
  * One communicator per process/GPU.  librccl is opened on the first call (dlopen; not a link-time dependency).

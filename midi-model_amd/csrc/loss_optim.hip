@@ -1,6 +1,7 @@
 // Cross-entropy over the vocabulary, gradient-norm clip + AdamW, and the grammar-masked softmax of the
 // sampler.  All HBM-bound row / flat-buffer streamers; reductions are deterministic (no float atomics).
 #include "common.h"
+#include "philox.h"
 
 #define DISPATCH_T(dtype, CALL)                                    \
   do {                                                             \
@@ -580,6 +581,27 @@ constexpr int SAMPLE_MAX_RANGE = 2048;
 // arithmetic in the same order, same id.  top_k[b] is clamped into [1, min(SAMPLE_MAX_K, V)] before any use (the q row read,
 // sel_v / sel_i / wl, the readlane loops): whatever the arrays hold, no access leaves its buffer.  The two strides are read by
 // ROWS instantiations only.
+//
+// SEEDED (mh_sample_top_p_k_seeded; a decode pool with a seed per request): ROWS, with the variate of rank j COMPUTED where the other
+// forms load q[b, j] -- philox::exp1_variate(seed[b], ctr[b], pos, j), a counter-based generator evaluated by the top_k lanes that
+// need a variate, so a row's noise depends on its own seed and event index and on nothing a batch mate does.  seed[b] and ctr[b]
+// are block-uniform scalar loads like temp[b]; the ten rounds touch no memory and stand right behind the requests of the candidate
+// logits and masks, ahead of the softmax pass: under load latency (with them in FRONT of those requests hipcc kept them there, and
+// wave 0 asked for its logits ~100 instructions late).  Everything past qv is the code of the other forms.  The q argument of this form is the pair of
+// arrays, so the other forms keep their argument list -- and their code: philox.h is reached by SEEDED instantiations only.
+struct SeededNoise {
+  const uint64_t* __restrict__ seed;  // [B] request seeds
+  const int32_t* __restrict__ ctr;    // [B] index of the event being sampled in the request's result
+};
+template <bool SEEDED>
+struct SampleNoise {
+  using Q = const float* __restrict__;
+};
+template <>
+struct SampleNoise<true> {
+  using Q = SeededNoise;
+};
+
 template <bool ROWS>
 struct SampleArg {  // how the kernel receives temp / top_p / top_k: by value, or per row from device memory
   using F = float;
@@ -591,14 +613,14 @@ struct SampleArg<true> {
   using I = const int32_t* __restrict__;
 };
 
-template <typename T, int TMAX, bool ROWS = false>  // TMAX: candidates per lane (64 * TMAX >= the longest mask range of this position)
+template <typename T, int TMAX, bool ROWS = false, bool SEEDED = false>  // TMAX: candidates per lane (64 * TMAX >= the longest mask range of this position)
 __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict__ logits, int64_t ldl,
                                                              const uint8_t* __restrict__ first_mask,
                                                              const uint8_t* __restrict__ ban_mask,
                                                              const int32_t* __restrict__ lo_tab,
                                                              const int32_t* __restrict__ hi_tab, int tab_stride,
                                                              const int64_t* __restrict__ ev, int pos, int first_lo,
-                                                             int first_hi, const float* __restrict__ q,
+                                                             int first_hi, typename SampleNoise<SEEDED>::Q q,
                                                              int64_t* __restrict__ out, int64_t out_stride,
                                                              int64_t* __restrict__ out_b, int64_t* __restrict__ out_c,
                                                              int64_t B, int V, typename SampleArg<ROWS>::F temp_arg,
@@ -617,12 +639,19 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
   __shared__ unsigned long long wl[SPLIT ? 4 : 1][SAMPLE_MAX_K];
   // (every kernel argument fetched at entry in one batch: see attn_decode_kernel)
   asm volatile("" ::"s"(logits), "s"(ldl), "s"(first_mask), "s"(ban_mask), "s"(lo_tab), "s"(hi_tab), "s"(tab_stride), "s"(ev));
-  asm volatile("" ::"s"(pos), "s"(first_lo), "s"(first_hi), "s"(q), "s"(out), "s"(out_stride), "s"(out_b), "s"(out_c));
+  static_assert(ROWS || !SEEDED, "the seeded sampler is a form of the per-row sampler");
+  if constexpr (SEEDED) {
+    asm volatile("" ::"s"(pos), "s"(first_lo), "s"(first_hi), "s"(q.seed), "s"(q.ctr), "s"(out), "s"(out_stride), "s"(out_b), "s"(out_c));
+  } else {
+    asm volatile("" ::"s"(pos), "s"(first_lo), "s"(first_hi), "s"(q), "s"(out), "s"(out_stride), "s"(out_b), "s"(out_c));
+  }
   asm volatile("" ::"s"(V), "s"(temp_arg), "s"(top_p_arg), "s"(top_k_arg), "s"(fill_rest), "s"(fill_id));
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t b = blockIdx.x;
   float temp, top_p;
   int top_k;
+  [[maybe_unused]] uint64_t row_seed = 0;
+  [[maybe_unused]] int32_t row_ctr = 0;
   if constexpr (ROWS) {
     asm volatile("" ::"s"(first_stride), "s"(ban_stride));
     // this row's values.  Read through the constant address space: the kernel never writes the three arrays, and that is what
@@ -633,6 +662,11 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
     temp = *(ConstF)(uintptr_t)(temp_arg + b);
     top_p = *(ConstF)(uintptr_t)(top_p_arg + b);
     top_k = *(ConstI)(uintptr_t)(top_k_arg + b);
+    if constexpr (SEEDED) {  // (requested with the three above; used by wave 0 below)
+      typedef const __attribute__((address_space(4))) uint64_t* ConstU64;
+      row_seed = *(ConstU64)(uintptr_t)(q.seed + b);
+      row_ctr = *(ConstI)(uintptr_t)(q.ctr + b);
+    }
     const int kmax = V < SAMPLE_MAX_K ? V : SAMPLE_MAX_K;
     top_k = top_k < 1 ? 1 : (top_k > kmax ? kmax : top_k);
     first_mask += b * first_stride;
@@ -648,7 +682,9 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
   int l = first_lo, h = first_hi;
   const int t0 = SPLIT ? wave * TW : 0;  // this wave's first candidate slot
   if (SPLIT || wave == 0) {
-    if (wave == 0 && lane < top_k) qv = q[b * (int64_t)V + lane];
+    if constexpr (!SEEDED) {
+      if (wave == 0 && lane < top_k) qv = q[b * (int64_t)V + lane];
+    }
     if (pos > 0) {
       const int64_t e = ev[b];
       l = lo_tab[e * tab_stride + pos];
@@ -667,6 +703,12 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
       zraw[t] = row[c];
       fm[t] = first_mask[c];
       bm[t] = ban_mask[c];  // (always a real mask: an optional pointer costs a branch + wait per element here)
+    }
+    if constexpr (SEEDED) {  // the variate of this lane's rank: registers only, behind the requests above and under their latency
+      if (wave == 0 && lane < top_k) {
+        uint32_t bits;
+        qv = philox::exp1_variate(row_seed, row_ctr, pos, lane, &bits);
+      }
     }
 #pragma unroll
     for (int t = 0; t < TW; ++t) {
@@ -915,6 +957,64 @@ extern "C" int mh_sample_top_p_k_rows(const void* logits, int64_t ldl, const uin
   else if (span <= 512) MH_SAMPLE_ROWS(8);
   else MH_SAMPLE_ROWS(32);
 #undef MH_SAMPLE_ROWS
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// The seeded form: the per-row form with row b's Exp(1) variates computed from (seed[b], ctr[b], pos, rank) inside the kernel.
+extern "C" int mh_sample_top_p_k_seeded(const void* logits, int64_t ldl, const uint8_t* first_mask, int64_t first_stride,
+                                        const uint8_t* ban_mask, int64_t ban_stride, int first_lo, int first_hi,
+                                        const int32_t* lo_tab, const int32_t* hi_tab, int tab_stride, int max_range,
+                                        const int64_t* ev, int pos, const uint64_t* seed, const int32_t* ctr, int64_t* out,
+                                        int64_t out_stride, int64_t* out_b, int64_t* out_c, int64_t B, int V, const float* temp,
+                                        const float* top_p, const int32_t* top_k, int fill_rest, int64_t fill_id, int dtype,
+                                        void* stream) {
+  MH_REQUIRE(B > 0 && V > 0 && pos >= 0 && pos < tab_stride && fill_rest >= 0 && fill_rest < out_stride,
+             "sample_top_p_k_seeded: bad args");
+  MH_REQUIRE(temp != nullptr && top_p != nullptr && top_k != nullptr,
+             "sample_top_p_k_seeded: temp, top_p (float [B]) and top_k (int32 [B]) are device arrays and required");
+  MH_REQUIRE(seed != nullptr, "sample_top_p_k_seeded: seed (uint64 [B], device) is required");
+  MH_REQUIRE(ctr != nullptr, "sample_top_p_k_seeded: ctr (int32 [B], device) is required");
+  MH_REQUIRE(first_mask != nullptr && ban_mask != nullptr,
+             "sample_top_p_k_seeded: first_mask and ban_mask (V bytes per row; all zero = nothing banned) are required");
+  MH_REQUIRE(first_stride >= 0 && ban_stride >= 0, "sample_top_p_k_seeded: negative mask stride");
+  MH_REQUIRE(pos == 0 || (ev != nullptr && lo_tab != nullptr && hi_tab != nullptr), "sample_top_p_k_seeded: position %d needs the event ids and range tables", pos);
+  MH_REQUIRE(first_lo >= 0 && first_hi <= V && first_hi - first_lo <= SAMPLE_MAX_RANGE && max_range <= SAMPLE_MAX_RANGE,
+             "sample_top_p_k_seeded: a grammar mask spans more than %d ids (first %d..%d, parameters %d)", SAMPLE_MAX_RANGE,
+             first_lo, first_hi, max_range);
+  const int span = pos == 0 ? first_hi - first_lo : max_range;
+  const SeededNoise noise{seed, ctr};
+#define MH_SAMPLE_SEEDED(TMAX_)                                                                                           \
+  DISPATCH_T(dtype, (sample_top_p_k_kernel<T, TMAX_, true, true><<<(int)B, 256, 0, (hipStream_t)stream>>>(               \
+                        (const T*)logits, ldl, first_mask, ban_mask, lo_tab, hi_tab, tab_stride, ev, pos, first_lo, first_hi, noise, out, \
+                        out_stride, out_b, out_c, B, V, temp, top_p, top_k, fill_rest, fill_id, first_stride, ban_stride)))
+  if (span <= 128) MH_SAMPLE_SEEDED(2);
+  else if (span <= 512) MH_SAMPLE_SEEDED(8);
+  else MH_SAMPLE_SEEDED(32);
+#undef MH_SAMPLE_SEEDED
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// The generator of the seeded form alone: word 0 of the Philox block and the variate made of it, for the 64 ranks of every row,
+// through the device function the sampler calls.  One wave per row.
+__global__ __launch_bounds__(64) void sample_noise_seeded_kernel(const uint64_t* __restrict__ seed, const int32_t* __restrict__ ctr,
+                                                                 int pos, uint32_t* __restrict__ bits, float* __restrict__ q) {
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x;
+  uint32_t x;
+  const float qv = philox::exp1_variate(seed[b], ctr[b], pos, lane, &x);
+  bits[b * SAMPLE_MAX_K + lane] = x;
+  q[b * SAMPLE_MAX_K + lane] = qv;
+}
+
+extern "C" int mh_sample_noise_seeded(const uint64_t* seed, const int32_t* ctr, int pos, int64_t B, uint32_t* bits, float* q,
+                                      void* stream) {
+  MH_REQUIRE(B > 0 && B <= 0x7fffffff && pos >= 0, "sample_noise_seeded: bad args");
+  MH_REQUIRE(seed != nullptr, "sample_noise_seeded: seed (uint64 [B], device) is required");
+  MH_REQUIRE(ctr != nullptr, "sample_noise_seeded: ctr (int32 [B], device) is required");
+  MH_REQUIRE(bits != nullptr && q != nullptr, "sample_noise_seeded: bits (uint32 [B, 64]) and q (float [B, 64]) are required");
+  sample_noise_seeded_kernel<<<(int)B, SAMPLE_MAX_K, 0, (hipStream_t)stream>>>(seed, ctr, pos, bits, q);
   MH_LAUNCH_CHECK();
   return MH_OK;
 }

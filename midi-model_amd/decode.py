@@ -44,6 +44,15 @@ addresses, not values, and the pool key holds no sampling parameter: one session
 a new setting is B-element copies (set_row_params, set_limit) instead of a new K/V cache and three captures.  The form has no
 op-by-op sampler behind it: it needs the fused kernel (grammar spans of at most 2048 ids, top_k <= 64).
 
+``seeded`` (row_params only; generate_ragged(seed=...), decode_pool(seeded=True)): a seed per row in ``seed_rows`` (int64 [B]: the 64
+bits), and the token steps call mh_sample_top_p_k_seeded with ``seed_rows`` and ``pos`` -- row b's variate at token position i for
+rank j is Philox4x32-10 of (pos[b], i, j) under seed_rows[b], computed by the lanes that need one.  ``pos[b]`` is the index of the
+event being sampled in row b's result (prompt events + events generated so far): the token steps of an event run before the net
+body advances it.  Such a session has no ``q_all``, no noise graph, no noise stream and no generator (``gen is None``):
+``draw_noise`` / ``consumed`` do nothing, ``begin`` / ``end`` touch no generator, one event is TWO graph replays.  The graphs read
+both arrays at replay time, so a new seed is a B-element copy (``set_row_seeds``) or one more section of an admission's block.  Its
+pool key carries "seeded": an unseeded session is never handed out in its place, and no existing key changes.
+
 ``admit`` / ``release`` (row_params sessions; pool.DecodePool drives them): rows of a RUNNING batch change hands between two
 events.  ``admit(rows, ...)`` runs one packed forward over the new prompts alone, stores their K/V into cache rows ``rows``
 (mh_kv_store_seqs_rows) and overwrites those rows of ``hidden``, ``pos``, ``pos_limit``, the three sampler arrays and the two masks;
@@ -90,14 +99,15 @@ def graphs_enabled(device: torch.device) -> bool:
 
 class DecodeSession:
     def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int, shared_capacity: int = 0,
-                 ragged: bool = False, row_params: bool = False):
+                 ragged: bool = False, row_params: bool = False, seeded: bool = False):
         tok = model.tokenizer
         self.model, self.B, self.cap, self.temp = model, B, capacity, float(temp)
         self.top_p, self.top_k = float(top_p), int(top_k)
         self.shared_capacity = int(shared_capacity)
         self.ragged = bool(ragged)
         self.row_params = bool(row_params)
-        self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params)
+        self.seeded = bool(seeded)
+        self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params, seeded)
         dev, dt = model.device, model.dtype
         self.T, self.V, self.Vp = tok.max_token_seq, tok.vocab_size, model.vocab_padded
         spec, tspec = model._specs["net"], model._specs["net_token"]
@@ -130,6 +140,8 @@ class DecodeSession:
             self.top_k_rows = torch.full((B,), self.top_k, dtype=torch.int32, device=dev)
             self.first_mask = first[None, :].repeat(B, 1)
             self.ban = torch.zeros_like(self.first_mask)
+        # (seeded) row b's seed, the 64 bits in int64 storage; zeros until set_row_seeds / admit writes a request's
+        self.seed_rows = torch.zeros((B,), dtype=torch.int64, device=dev) if self.seeded else None
         # cached events so far (device side); ragged: per row, and the position a row is parked at (the call's max_len)
         self.pos = torch.zeros(B if self.ragged else 1, dtype=torch.int32, device=dev)
         self.pos_limit = torch.zeros(B if self.row_params else 1, dtype=torch.int32, device=dev) if self.ragged else None
@@ -141,8 +153,9 @@ class DecodeSession:
         self.neg1 = torch.full((B,), -1, dtype=torch.int32, device=dev)
         self.probs = torch.zeros((B, 1, self.V), dtype=torch.float32, device=dev)
         # Exp(1) noise of the sampler, one [B, V] slice per token position (ones: a step sampled before any draw is greedy-safe)
-        self.q_all = torch.ones((self.T, B, self.V), dtype=torch.float32, device=dev)
-        self.q = self.q_all[0]
+        # (a seeded session has none: its sampler computes the variates it needs)
+        self.q_all = None if self.seeded else torch.ones((self.T, B, self.V), dtype=torch.float32, device=dev)
+        self.q = None if self.seeded else self.q_all[0]
         self.logits = torch.zeros((B, self.Vp), dtype=dt, device=dev)
         # RMSNorm weights folded into the projections that follow them (one launch for norm + projection)
         self.fold1 = self.fold2 = self.lm_fold = None
@@ -160,7 +173,8 @@ class DecodeSession:
         self.g_tok: List[Optional[torch.cuda.CUDAGraph]] = [None] * self.T
         self.g_noise = self.g_steps = None
         self.use_graphs = graphs_enabled(dev)
-        self.gen = torch.Generator(device=dev) if self.use_graphs else None  # the generator the captured sampler draws from
+        # the generator the captured sampler draws from (a seeded session draws from none)
+        self.gen = torch.Generator(device=dev) if self.use_graphs and not self.seeded else None
         self._user_gen = None
         self._admit_stage = None   # the pinned host block of the last admission (admit)
         self._pool = None
@@ -174,15 +188,18 @@ class DecodeSession:
             self._capture()
 
     @staticmethod
-    def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False, row_params=False):
+    def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False, row_params=False, seeded=False):
         if ragged and shared_capacity:
             raise ValueError("DecodeSession: ragged rows have prompts of their own -- not together with a shared prompt")
+        if seeded and not (ragged and row_params):
+            raise ValueError("DecodeSession: seeded is a form of the per-row session -- it needs ragged=True, row_params=True")
         if row_params:
             if shared_capacity or not ragged:
                 raise ValueError("DecodeSession: row_params is a form of the ragged session -- not with a shared prompt, not "
                                  "without ragged=True")
-            # no temperature, top-p or top-k: they are buffer contents of this form, not facts of its graphs
-            return (model._flat.data_ptr(), model._flat.dtype, B, capacity, ("ragged", "row_params"))
+            # no temperature, top-p or top-k: they are buffer contents of this form, not facts of its graphs (nor is a seed)
+            form = ("ragged", "row_params", "seeded") if seeded else ("ragged", "row_params")
+            return (model._flat.data_ptr(), model._flat.dtype, B, capacity, form)
         key = (model._flat.data_ptr(), model._flat.dtype, B, capacity, float(temp), float(top_p), int(top_k))
         if ragged:
             return key + (("ragged",),)
@@ -253,6 +270,12 @@ class DecodeSession:
             # one launch instead of sample_top_p_k's ~25: the Exp(1) noise torch.multinomial would draw internally
             # (empty_like(probs).exponential_(1, generator)) is drawn here (eager form) or by the noise graph ahead of the
             # step (draw=False), the rest is mh_sample_top_p_k
+            if self.seeded:  # nothing is drawn: row b's variates follow from seed_rows[b] and pos[b], the index of this event
+                ops.sample_top_p_k_seeded(self.logits, self.first_mask, self.lo_tab, self.hi_tab, self.ev, i, self.seed_rows, self.pos,
+                                          self.seq[:, i], self.V, self.temp_rows, self.top_p_rows, self.top_k_rows, self.ban,
+                                          out_b=self.samples_in, out_c=self.ev if i == 0 else None, first_span=self.first_span,
+                                          max_range=self.max_range[i], fill_rest=self.T - 1 if i == 0 else 0, fill_id=self.pad_id)
+                return
             if draw:
                 self.q_all[i].exponential_(1.0, generator=generator)
             if self.row_params:  # the same kernel, row b on temp_rows[b], top_p_rows[b], top_k_rows[b] and its own two masks
@@ -298,7 +321,16 @@ class DecodeSession:
         self.g_net = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.g_net, pool=pool, capture_error_mode="thread_local"):
             self._net_body()
-        if self.fused_sampler:
+        if self.seeded:
+            # all T token steps in one graph; no noise graph, no noise stream: the sampler computes its variates
+            self.g_steps = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.g_steps, pool=pool, capture_error_mode="thread_local"):
+                for i in range(self.T):
+                    self._tok_body(i, draw=False)
+            self.copy_stream = torch.cuda.Stream()
+            self.steps_done = torch.cuda.Event()
+            self.seq_host = torch.empty((self.B, self.T), dtype=torch.long).pin_memory()
+        elif self.fused_sampler:
             # the event's draws in one graph (the only one that touches the generator) ...
             self.g_noise = torch.cuda.CUDAGraph()
             self.g_noise.register_generator_state(self.gen)  # philox seed/offset are read at replay time, offsets advance per replay
@@ -403,6 +435,24 @@ class DecodeSession:
         self.top_p_rows.copy_(torch.tensor(vals[1], dtype=torch.float32))
         self.top_k_rows.copy_(torch.tensor(vals[2], dtype=torch.int32))
 
+    @staticmethod
+    def _seed_values(seeds, n: int, what: str) -> list:
+        """n Python ints in [0, 2^64) -> their int64 storage values (the same 64 bits); ValueError otherwise"""
+        seeds = list(seeds) if seeds is not None else None
+        if seeds is None or len(seeds) != n:
+            raise ValueError(f"{what}: {'no' if seeds is None else len(seeds)} seeds for {n} rows")
+        for s in seeds:
+            if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < (1 << 64):
+                raise ValueError(f"{what}: seed {s!r} is not an integer in [0, 2^64)")
+        from .ops_seeded import seed_storage
+        return seed_storage(seeds)
+
+    def set_row_seeds(self, seeds) -> None:
+        """(seeded) row b samples on seeds[b] from now on: one B-element copy into the buffer the captured sampler reads"""
+        if not self.seeded:
+            raise ValueError("set_row_seeds: not a seeded session")
+        self.seed_rows.copy_(torch.tensor(self._seed_values(seeds, self.B, "set_row_seeds"), dtype=torch.int64))
+
     def prefill_ragged(self, tokens: torch.Tensor, lengths) -> None:
         """tokens [M, T]: the B prompts laid end to end, prompt b of lengths[b] events.  One packed causal forward from empty
         caches (engine.stack_prefill_seqs); leaves hidden[b] = prompt b's last position and pos[b] = lengths[b].  Prompts of one
@@ -436,7 +486,7 @@ class DecodeSession:
         self.hidden.copy_(y.index_select(0, plan.seq_start[1:].long() - 1))
         self.pos.copy_(plan.seq_start[1:] - plan.seq_start[:-1])
 
-    def admit(self, rows, tokens: torch.Tensor, lengths, limits, temp, top_p, top_k, first_masks, bans) -> None:
+    def admit(self, rows, tokens: torch.Tensor, lengths, limits, temp, top_p, top_k, first_masks, bans, seeds=None) -> None:
         """(row_params) n new requests into rows ``rows`` of the running batch, between two events (the header has the stream-order
         argument).  tokens [M, T]: the n prompts laid end to end, prompt s of lengths[s] events; limits[s]: the position row
         rows[s] is parked at (its max_len); temp / top_p / top_k: n values; first_masks / bans: uint8 [n, V] (host).  ONE packed
@@ -444,8 +494,9 @@ class DecodeSession:
         request's prefill depends on its admission group through that forward's own shape dispatch and through nothing else --
         K/V into cache rows ``rows``, hidden[rows] = each prompt's last position, pos[rows] = lengths, and pos_limit, the sampler
         arrays and both masks of those rows overwritten.  The per-row values travel in ONE pinned host block and are scattered by
-        eight index_copy_ calls (and one index_select for the last positions): no kernel of their own.  Everything is checked
-        on the host first; ``ValueError`` before any launch."""
+        eight index_copy_ calls (and one index_select for the last positions): no kernel of their own.  A seeded session takes
+        ``seeds`` as well, n ints in [0, 2^64): one more int64 section of the block and a ninth index_copy_ into ``seed_rows``; an
+        unseeded session refuses them.  Everything is checked on the host first; ``ValueError`` before any launch."""
         if not (self.ragged and self.row_params):
             raise ValueError("DecodeSession.admit: rows are admitted into a ragged=True, row_params=True session only")
         from .ops_pool import check_rows
@@ -469,11 +520,17 @@ class DecodeSession:
         for name, t in (("first_masks", first_masks), ("bans", bans)):
             if t.dtype != torch.uint8 or t.shape != (n, V) or t.device.type != "cpu":
                 raise ValueError(f"admit: {name} must be a host uint8 tensor [{n}, {V}]: {t.dtype} {tuple(t.shape)} on {t.device}")
+        if self.seeded:
+            seed_vals = self._seed_values(seeds, n, "admit")
+        elif seeds is not None:
+            raise ValueError("admit: seeds are taken by a seeded=True session only")
         # ---- the one host block: [idx i64 | last i64 | rows i32 | lengths i32 | limits i32 | top_k i32 | temp f32 | top_p f32 |
-        #      first u8 | ban u8], every section on a multiple of 16 bytes
+        #      first u8 | ban u8 (| seeds i64)], every section on a multiple of 16 bytes
         sections = [(np.int64, ids), (np.int64, np.cumsum(lengths) - 1), (np.int32, ids), (np.int32, lengths), (np.int32, limits),
                     (np.int32, vals[2]), (np.float32, vals[0]), (np.float32, vals[1]),
                     (np.uint8, first_masks.numpy().reshape(-1)), (np.uint8, bans.numpy().reshape(-1))]
+        if self.seeded:
+            sections.append((np.int64, seed_vals))
         parts, offs, at = [], [], 0
         for ty, v in sections:
             a = np.ascontiguousarray(np.asarray(v, dtype=ty)).view(np.uint8)
@@ -492,6 +549,7 @@ class DecodeSession:
                torch.uint8, torch.uint8)
         idx, last, rows_dev, len_dev, lim_dev, k_dev, t_dev, p_dev, first_dev, ban_dev = \
             (block[o:o + sz].view(ty) for ty, (o, sz) in zip(tys, offs))
+        seed_dev = block[offs[10][0]:offs[10][0] + offs[10][1]].view(torch.int64) if self.seeded else None
         # ---- one packed forward over the admitted prompts alone, K/V into the chosen cache rows
         plan = ops.attn_seq_plan(lengths, spec.H).upload(dev)
         e = torch.empty((M, spec.D), dtype=m.dtype, device=dev)
@@ -507,6 +565,8 @@ class DecodeSession:
         self.top_k_rows.index_copy_(0, idx, k_dev)
         self.first_mask.index_copy_(0, idx, first_dev.view(n, V))
         self.ban.index_copy_(0, idx, ban_dev.view(n, V))
+        if self.seeded:
+            self.seed_rows.index_copy_(0, idx, seed_dev)
 
     def release(self, rows) -> None:
         """(row_params) rows whose requests have finished: pos = pos_limit = 0 there.  A free row is still embedded, attended and
@@ -523,7 +583,10 @@ class DecodeSession:
         self.pos_limit.index_fill_(0, idx, 0)
 
     def begin(self, generator) -> None:
-        """take over the caller's random stream (None = the device's default generator)"""
+        """take over the caller's random stream (None = the device's default generator).  A seeded session has no generator of its
+        own (``gen is None``) and takes none: here and in ``end`` nothing reads or writes a generator's state."""
+        if self.seeded and generator is not None:
+            raise ValueError("DecodeSession.begin: a seeded session draws nothing from a generator")
         self._user_gen = generator
         self._noise_pending = False
         self._noise_read = False
@@ -649,7 +712,8 @@ class DecodeSession:
             if not self._noise_pending:
                 self.draw_noise()
             cur = torch.cuda.current_stream()
-            cur.wait_event(self.noise_done)
+            if self.g_noise is not None:  # (a seeded session has no noise to wait for)
+                cur.wait_event(self.noise_done)
             self.g_steps.replay()
             self.steps_done.record(cur)
             self._steps_recorded = True

@@ -501,7 +501,7 @@ class MIDIModel(nn.Module):
                                      disable_patch_change, disable_control_change, disable_channels, shared)
 
     def generate_ragged(self, prompts, max_len=512, temp=1.0, top_p=0.98, top_k=20, disable_patch_change=False,
-                        disable_control_change=False, disable_channels=None, generator=None, ban_eos: bool = False):
+                        disable_control_change=False, disable_channels=None, generator=None, ban_eos: bool = False, seed=None):
         """(ours) ``generate`` for B prompts of B DIFFERENT lengths in ONE decode batch: ``prompts`` is a sequence of B arrays, row
         b of shape ``(L_b, T')``, 1 <= T' <= 8, padded and range-checked as ``generate`` pads and checks its prompt.  Returns a
         list of B ``np.ndarray (<= max_len, 8) int64``, row b with its prompt in front.
@@ -529,8 +529,14 @@ class MIDIModel(nn.Module):
         any launch: a sequence whose length is not B; a temperature that is not finite or not above 0; a NaN ``top_p``; a
         ``top_k`` outside [1, min(64, V)] (the scalar path keeps its op-by-op sampler for larger k, this form has none); row b's
         prompt holding ``max_len[b]`` events or more (the message names the row); per row, what the mask options refuse.
-        Out of scope: a generator per row (a row's draws depend on its batch mates: they share the ``[8, B, V]`` stream); per-row
-        values on ``generate`` / ``generate_stream`` / ``share_prompt``.  Admitting new rows into a running batch is not this call's
+        A SEED per row: ``seed`` is a sequence of B Python ints in [0, 2^64).  The call then runs on a ``seeded`` row_params session
+        (decode.py): no ``[8, B, V]`` noise and no generator -- ``seed`` together with ``generator`` is a ``ValueError`` -- the
+        sampler computes row b's variates from (seed[b], the index of the event in row b's result, token position, rank)
+        (``mh_sample_top_p_k_seeded``), so row b's ids no longer depend on its batch mates' draws or on its row number.  The
+        stated limits are pool.py's: the promise holds at equal launch shapes (the same B; the same prompts prefilled together).
+        ``bool``, floats, negatives and a wrong length are refused, the message naming the row.  ``seed=None``: everything above.
+        Out of scope: per-row values on ``generate`` / ``generate_stream`` / ``share_prompt``.
+        Admitting new rows into a running batch is not this call's
         job: ``decode_pool`` / ``generate_pool`` do that (pool.py).
         The prompts are prefilled packed -- no padded event is computed; prompts of ONE length are prefilled by
         ``generate``'s uniform forward, so that for the same seeded generator the call returns exactly ``generate``'s ids.
@@ -539,7 +545,7 @@ class MIDIModel(nn.Module):
         ~210 launches for 1 row as for 64, so B lengths in one batch should approach B times the useful events/s of B batches
         of one; the net graph gains two tiny launches (the position update) and nothing else."""
         rp = self._row_params(prompts, max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change,
-                              disable_channels)
+                              disable_channels, seed, generator)
         rows = self._ragged_prompts(prompts, max_len if rp is None else rp["max_len"], None)
         chans = None if rp is not None else \
             self._check_mask_options(ban_eos, disable_patch_change, disable_control_change, disable_channels)
@@ -551,12 +557,13 @@ class MIDIModel(nn.Module):
         return [np.concatenate(o, axis=0) for o in outs]
 
     def generate_stream_ragged(self, prompts, max_len=512, temp=1.0, top_p=0.98, top_k=20, disable_patch_change=False,
-                               disable_control_change=False, disable_channels=None, generator=None, ban_eos: bool = False):
+                               disable_control_change=False, disable_channels=None, generator=None, ban_eos: bool = False,
+                               seed=None):
         """The serving form of ``generate_ragged``: a Python generator that yields, per event step, ``(events np.int64 (B, 8),
         live np.bool_ (B,))`` -- row b of ``events`` counts only where ``live[b]``.  Each prompt is cropped to its last 4096
         events first, as ``generate_stream`` crops.  The arguments are checked HERE, before the generator is handed out."""
         rp = self._row_params(prompts, max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change,
-                              disable_channels)
+                              disable_channels, seed, generator)
         rows = self._ragged_prompts(prompts, max_len if rp is None else rp["max_len"], 4096)
         chans = None if rp is not None else \
             self._check_mask_options(ban_eos, disable_patch_change, disable_control_change, disable_channels)
@@ -568,15 +575,18 @@ class MIDIModel(nn.Module):
         return isinstance(x, (list, tuple)) or (isinstance(x, (np.ndarray, torch.Tensor)) and x.ndim > 0)
 
     def _row_params(self, prompts, max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change,
-                    disable_channels):
+                    disable_channels, seed=None, generator=None):
         """The arguments of generate_ragged that take a value per row, checked on the host before any launch.  -> None when every
         one of them is the call's (scalars; a flat list of channels): today's path.  Otherwise a dict of B-element lists -- scalars
-        repeated -- under the argument names, ``chans`` holding row b's sorted banned channels; every refusal is a ValueError."""
+        repeated -- under the argument names, ``chans`` holding row b's sorted banned channels; every refusal is a ValueError.
+        ``seed`` (not None: B ints in [0, 2^64), row b's seed) always gives the dict, with the checked seeds under ``"seed"``."""
         channels_per_row = self._per_row(disable_channels) and any(c is None or self._per_row(c) for c in disable_channels)
         scalars = dict(max_len=max_len, temp=temp, top_p=top_p, top_k=top_k, ban_eos=ban_eos,
                        disable_patch_change=disable_patch_change, disable_control_change=disable_control_change)
-        if not channels_per_row and not any(self._per_row(v) for v in scalars.values()):
+        if seed is None and not channels_per_row and not any(self._per_row(v) for v in scalars.values()):
             return None
+        if seed is not None and generator is not None:
+            raise ValueError("generate_ragged: seed and generator together -- a seeded call draws nothing from a generator")
         if prompts is None or len(prompts) == 0:
             raise ValueError("generate_ragged: no prompts")
         B = len(prompts)
@@ -609,6 +619,15 @@ class MIDIModel(nn.Module):
                 raise ValueError(f"row {b}: {e}") from None
         rp["max_len"] = [int(n) for n in rp["max_len"]]
         rp["top_k"] = [int(k) for k in rp["top_k"]]
+        if seed is not None:
+            if not self._per_row(seed) or len(seed) != B:
+                raise ValueError(f"generate_ragged: seed must be a sequence of {B} integers, one per prompt"
+                                 + (f": it holds {len(seed)}" if self._per_row(seed) else ""))
+            seed = seed.tolist() if isinstance(seed, (np.ndarray, torch.Tensor)) else list(seed)
+            for b, s in enumerate(seed):
+                if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < (1 << 64):
+                    raise ValueError(f"generate_ragged: row {b}: seed {s!r} is not an integer in [0, 2^64)")
+            rp["seed"] = [int(s) for s in seed]
         return rp
 
     def _ragged_prompts(self, prompts, max_len, crop) -> list:
@@ -648,7 +667,8 @@ class MIDIModel(nn.Module):
             if rp is not None:
                 max_len = np.array(rp["max_len"], dtype=np.int64)
                 # (1.0, 0.98, 1 fill a NEW session's buffers through its warm-up pass; set_row_params below overwrites them)
-                ses = self._checkout_session(B, int(max_len.max()) + 1, 1.0, 0.98, 1, ragged=True, row_params=True)
+                ses = self._checkout_session(B, int(max_len.max()) + 1, 1.0, 0.98, 1, ragged=True, row_params=True,
+                                             seeded="seed" in rp)
             else:
                 ses = self._checkout_session(B, max_len + 1, float(temp), float(top_p), int(top_k), ragged=True)
         try:
@@ -656,6 +676,8 @@ class MIDIModel(nn.Module):
                 if rp is not None:
                     self._set_masks_rows(ses, rp)
                     ses.set_row_params(rp["temp"], rp["top_p"], rp["top_k"])
+                    if "seed" in rp:
+                        ses.set_row_seeds(rp["seed"])
                 else:
                     self._set_masks(ses, ban_eos, disable_patch_change, disable_control_change, chans)
                 ses.reset()
@@ -777,7 +799,7 @@ class MIDIModel(nn.Module):
         ses.ban.copy_(ban)
 
     def _check_request(self, prompt, max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change,
-                       disable_channels, crop=4096):
+                       disable_channels, crop=4096, seed=None):
         """ONE request of a decode pool, checked as generate_ragged checks a row with values of its own (_row_params,
         _check_mask_options, _ragged_prompts: their code, their ValueErrors, before any launch) -> (prompt (L, 8) int64 cropped to
         its last ``crop`` events, the one-row dict of _row_params)"""
@@ -786,22 +808,27 @@ class MIDIModel(nn.Module):
         if disable_channels is not None and (not self._per_row(disable_channels) or any(
                 c is None or self._per_row(c) for c in disable_channels)):
             raise ValueError("a request's disable_channels is None or a flat sequence of channel numbers")
+        if self._per_row(seed):
+            raise ValueError("a request takes one seed: an integer in [0, 2^64)")
         rp = self._row_params([prompt], [max_len], [temp], [top_p], [top_k], [ban_eos], [disable_patch_change],
-                              [disable_control_change], [disable_channels])
+                              [disable_control_change], [disable_channels], None if seed is None else [seed])
         return self._ragged_prompts([prompt], rp["max_len"], crop)[0], rp
 
-    def decode_pool(self, rows: int, capacity: int, generator=None):
+    def decode_pool(self, rows: int, capacity: int, generator=None, seeded: bool = False):
         """(ours) a ``pool.DecodePool`` on this model: ``rows`` decode rows that requests are admitted into and released from
         while the batch runs (continuous batching).  ``capacity``: cache rows per decode row; a request needs
         max_len + 1 <= capacity (the session's own capacity is rounded up as every session's is, 256 x 2^k).  The pool takes one
         pooled ``row_params`` session at its first admission and holds it until ``close()`` (it is a context manager); it draws
-        from ``generator`` as ``generate_ragged`` does.  Nothing is launched here."""
+        from ``generator`` as ``generate_ragged`` does.  ``seeded=True``: every request brings a seed of its own
+        (``submit(seed=...)``) and the pool draws from no generator (pool.py has the promise and its limits); ``generator`` is
+        then refused.  Nothing is launched here."""
         from .pool import DecodePool
-        return DecodePool(self, rows, capacity, generator)
+        return DecodePool(self, rows, capacity, generator, seeded)
 
     def generate_pool(self, requests, rows: int, capacity: Optional[int] = None, generator=None) -> list:
         """(ours) ``requests``: a list of dicts, each the keyword arguments of ``DecodePool.submit`` (``prompt`` and any of max_len,
-        temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change, disable_channels).  They are submitted in order
+        temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change, disable_channels, seed).  If EVERY request
+        carries ``"seed"`` the pool is a seeded one; some with and some without is a ``ValueError``.  They are submitted in order
         to one pool of ``rows`` rows and stepped until all are done: a request waits only until a row is free, and a row that
         finishes is handed to the next request at once.  -> a list of ``np.ndarray (<= max_len, 8) int64``, request i's at index
         i, its prompt in front.  ``capacity`` defaults to the largest max_len + 1."""
@@ -810,7 +837,10 @@ class MIDIModel(nn.Module):
             return []
         if capacity is None:
             capacity = max(int(r.get("max_len", 512)) for r in requests) + 1
-        with self.decode_pool(rows, capacity, generator) as pool:
+        with_seed = sum("seed" in r and r["seed"] is not None for r in requests)
+        if with_seed not in (0, len(requests)):
+            raise ValueError(f"generate_pool: {with_seed} of {len(requests)} requests carry a seed -- all of them or none")
+        with self.decode_pool(rows, capacity, generator, seeded=with_seed > 0) as pool:
             ids = [pool.submit(**r) for r in requests]
             while pool.pending():
                 pool.step()
@@ -860,12 +890,13 @@ class MIDIModel(nn.Module):
 
     # decode sessions: buffers + captured graphs, one per concurrent generate() call (decode.py)
     def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int, shared_need: int = 0,
-                          ragged: bool = False, row_params: bool = False):
+                          ragged: bool = False, row_params: bool = False, seeded: bool = False):
         """``shared_need`` > 0: a shared-prompt session whose prompt cache holds shared_need events (capacities by the same
         doubling rule from 256, so one captured session serves a range of prompt and suffix lengths).  ``ragged``: a session
         with a position per row (generate_ragged), pooled like the others; not together with shared_need.  ``row_params``
         (ragged only): the session that reads temperature, top-p, top-k, masks and limit per row from its own buffers; its key
-        holds none of them, so temp / top_p / top_k only fill the buffers of a session built here."""
+        holds none of them, so temp / top_p / top_k only fill the buffers of a session built here.  ``seeded`` (row_params only):
+        the session whose sampler computes its noise from per-row seeds; a pooled session of its own kind."""
         from .decode import DecodeSession
         cap = 256
         while cap < need:
@@ -875,7 +906,7 @@ class MIDIModel(nn.Module):
             scap = 256
             while scap < shared_need:
                 scap *= 2
-        key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params)
+        key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded)
         pool = self._sessions
         with pool.lock:
             found = None
@@ -888,7 +919,7 @@ class MIDIModel(nn.Module):
         if found is not None:
             found.refresh()  # weights may have been trained / merged since the session derived its folded copies
             return found
-        return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params)
+        return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded)
 
     def _return_session(self, ses) -> None:
         with self._sessions.lock:

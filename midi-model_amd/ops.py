@@ -611,9 +611,14 @@ _GROUPED = ("wgrad_grouped", "wgrad_grouped_ok", "wgrad_grouped_operands_ok", "w
 _ROWS = ("sample_top_p_k_rows",)
 # ... and the packed K/V store into chosen rows of a live cache (ops_pool.py; stand-in in tests/emu_pool.py)
 _POOL = ("kv_store_seqs_rows",)
+# ... and the sampler with a seed per row, with its generator on its own (ops_seeded.py; stand-ins in tests/emu_seeded.py)
+_SEEDED = ("sample_top_p_k_seeded", "sample_noise_seeded")
 
 
 def __getattr__(name: str):
+    if name in _SEEDED:
+        from . import ops_seeded
+        return getattr(ops_seeded, name)
     if name in _POOL:
         from . import ops_pool
         return getattr(ops_pool, name)

@@ -24,9 +24,22 @@ occupied rows, free rows are sampled and dropped); a request that sampled EOS (i
 dozen tiny copies, a release two.  No graph is recaptured: the session's graphs read every per-row value from device
 memory.
 
+A SEED PER REQUEST (``model.decode_pool(rows, capacity, seeded=True)``, ``submit(..., seed=s)``, s an int in [0, 2^64)).  An
+unseeded pool's rows share the ``[8, B, V]`` noise of an event, so a sampled request's draws depend on its row and on the step it
+runs at: that pool is reproducible for the same generator seed AND the same submit / step schedule.  A seeded pool runs on a
+``seeded`` session (decode.py): no noise buffer, no noise graph, no generator; the sampler computes the variate of (request seed,
+index of the event in the request's result, token position, rank) with a counter-based generator (Philox4x32-10,
+``mh_sample_top_p_k_seeded``).  A request's ids are then a function of the weights, its prompt, its sampling settings, its seed
+and the SHAPES of the launches it runs in -- not of its row, the step it was admitted at, its neighbours, or what its row held
+before.  The stated limits of that promise:
+  * a request's prefill depends on its admission group through the packed forward's own shape dispatch (DecodeSession.admit);
+  * its decode steps depend on the session's row count through the projection kernels' dispatch;
+  * so the promise holds at equal launch shapes: the same pool size, and the same admission grouping or admitted alone.  At equal
+    shapes the kernels are bit-equal per row; nothing wider is claimed.
+Every request of a seeded pool needs a seed, an unseeded pool refuses one, and ``generator`` with ``seeded=True`` is refused.  Free
+and parked rows keep being sampled and dropped; their seeds are whatever the row last held.  Measured: DESIGN 7.8.
+
 Out of scope:
-  * a generator per request -- the rows share the ``[8, B, V]`` noise of an event, so a request's draws depend on its row and on
-    the step it runs at: the pool is reproducible for the same seed AND the same submit / step schedule, not per request;
   * a background thread or server loop -- the caller owns the loop (and the thread: one pool, one thread);
   * ``share_prompt`` inside the pool;
   * chunking a long admission: a 4096-event prefill on tv2o-medium is 4096 x 0.4 GFLOP of projections (12 layers x 16.8 M
@@ -53,7 +66,7 @@ import torch
 
 
 class _Request:
-    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done")
+    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done")  # (rp["seed"]: a seeded pool's request)
 
     def __init__(self, prompt: np.ndarray, rp: dict):
         self.prompt, self.rp, self.max_len = prompt, rp, rp["max_len"][0]
@@ -63,12 +76,15 @@ class _Request:
 
 
 class DecodePool:
-    """see the module docstring; made by ``MIDIModel.decode_pool(rows, capacity, generator)``"""
+    """see the module docstring; made by ``MIDIModel.decode_pool(rows, capacity, generator, seeded)``"""
 
-    def __init__(self, model, rows: int, capacity: int, generator=None):
+    def __init__(self, model, rows: int, capacity: int, generator=None, seeded: bool = False):
         if int(rows) != rows or rows < 1 or int(capacity) != capacity or capacity < 2:
             raise ValueError(f"decode_pool: {rows} rows of capacity {capacity}")
+        if seeded and generator is not None:
+            raise ValueError("decode_pool: seeded=True together with a generator -- a seeded pool draws nothing from a generator")
         self.model, self.rows, self.capacity, self.generator = model, int(rows), int(capacity), generator
+        self.seeded = bool(seeded)
         self.ses = None                                  # taken from the model's pool at the first admission
         self.free: List[int] = list(range(self.rows))    # ascending: the lowest free row is taken first
         self.queue: deque = deque()                      # request ids, FIFO
@@ -79,14 +95,19 @@ class DecodePool:
 
     # ---- the caller's side ----------------------------------------------------------------------------------------------
     def submit(self, prompt, max_len=512, temp=1.0, top_p=0.98, top_k=20, ban_eos=False, disable_patch_change=False,
-               disable_control_change=False, disable_channels=None) -> int:
+               disable_control_change=False, disable_channels=None, seed=None) -> int:
         """queue one request; -> its id.  Checked as ``generate_ragged`` checks a row with values of its own (the same code, the
         same ``ValueError``s), plus ``max_len + 1 > capacity``; the prompt is cropped to its last 4096 events, as the stream forms
-        crop.  Nothing is launched here."""
+        crop.  ``seed``: required in a seeded pool (an int in [0, 2^64)), refused in an unseeded one.  Nothing is launched here."""
         if self._closed:
             raise ValueError("DecodePool.submit: the pool is closed")
+        if self.seeded and seed is None:
+            raise ValueError("DecodePool.submit: every request of a seeded pool needs a seed (an integer in [0, 2^64))")
+        if not self.seeded and seed is not None:
+            raise ValueError("DecodePool.submit: this pool shares one noise stream among its rows; a seed per request needs "
+                             "decode_pool(..., seeded=True)")
         p, rp = self.model._check_request(prompt, max_len, temp, top_p, top_k, ban_eos, disable_patch_change,
-                                          disable_control_change, disable_channels)
+                                          disable_control_change, disable_channels, seed=seed)
         if rp["max_len"][0] + 1 > self.capacity:
             raise ValueError(f"DecodePool.submit: max_len {rp['max_len'][0]} in a pool of capacity {self.capacity} (max_len + 1 "
                              f"rows are needed)")
@@ -135,7 +156,8 @@ class DecodePool:
     def _session(self):
         if self.ses is None:
             # (1.0, 0.98, 1 fill a NEW session's buffers through its warm-up pass; every admission overwrites its rows')
-            ses = self.model._checkout_session(self.rows, self.capacity, 1.0, 0.98, 1, ragged=True, row_params=True)
+            ses = self.model._checkout_session(self.rows, self.capacity, 1.0, 0.98, 1, ragged=True, row_params=True,
+                                                seeded=self.seeded)
             ses.reset()                      # every row free: pos = pos_limit = 0
             ses.begin(self.generator)
             self.ses = ses
@@ -152,7 +174,7 @@ class DecodePool:
         first, ban = self.model._mask_rows(rp)
         tokens = torch.from_numpy(np.concatenate([r.prompt for r in reqs], axis=0))
         self._session().admit(rows, tokens, [len(r.prompt) for r in reqs], rp["max_len"], rp["temp"], rp["top_p"], rp["top_k"],
-                              first, ban)
+                              first, ban, seeds=rp.get("seed"))
         for row, rid, r in zip(rows, rids, reqs):
             r.row = row
             self.occupied[row] = rid

@@ -16,9 +16,15 @@ predicts: (useful + waste) / useful row-events -- the bound for a pool that is n
 drains (its last requests run beside free rows), so each arm reports the event steps it ran, its prefill groups and the time per
 step.  One JSON line on stdout (and in --out).
 
-usage: tools/bench_pool.py [--requests 256] [--rows 64] [--lmin 16] [--lmax 512] [--gmin 32] [--gmax 512] [--reps 3] [--out FILE]
+``--seeded``: the A/B is instead the SEEDED pool (decode_pool(seeded=True), request i on seed i: no noise graph, the sampler computes
+its variates) against the unseeded pool of (a) on the same request list, alternating in the same way; the same figures per arm,
+and ``seeded_over_pool`` (> 1: the seeded pool is faster).
 
-Result: profiles/pool_ab.txt when it holds a line of this tool (DESIGN 7.7 quotes it); NOT MEASURED otherwise."""
+usage: tools/bench_pool.py [--requests 256] [--rows 64] [--lmin 16] [--lmax 512] [--gmin 32] [--gmax 512] [--reps 3] [--seeded]
+                           [--out FILE]
+
+Result: profiles/pool_ab.txt when it holds a line of this tool (DESIGN 7.7 quotes it), profiles/seeded_ab.txt for --seeded (DESIGN
+7.8); NOT MEASURED otherwise."""
 import argparse
 import json
 import os
@@ -51,6 +57,7 @@ def main():
     ap.add_argument("--gmax", type=int, default=512)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--seeded", action="store_true", help="A/B the seeded pool against the unseeded pool")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -69,14 +76,16 @@ def main():
     waste = sum(max(gens[b] for b in grp) * len(grp) - sum(gens[b] for b in grp) for grp in groups)
     capacity = max(max_lens) + 1
 
-    def pool_run():
+    def pool_run(seeded=False):
         """-> (seconds, seconds to the first event of the last request, event steps, admission groups)"""
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         first_last = None
         got = steps = admissions = 0
-        with model.decode_pool(a.rows, capacity, generator=torch.Generator(device="cuda").manual_seed(1)) as pool:
-            ids = [pool.submit(p, max_len=m, ban_eos=True) for p, m in zip(prompts, max_lens)]
+        gen = None if seeded else torch.Generator(device="cuda").manual_seed(1)
+        with model.decode_pool(a.rows, capacity, generator=gen, seeded=seeded) as pool:
+            ids = [pool.submit(p, max_len=m, ban_eos=True, seed=i if seeded else None)
+                   for i, (p, m) in enumerate(zip(prompts, max_lens))]
             while pool.pending():
                 queued = len(pool.queue)
                 out = pool.step()
@@ -107,11 +116,13 @@ def main():
         assert got == useful, (got, useful)
         return t, first_last, steps, len(groups)
 
-    pool_run(), static_run()   # untimed: sessions captured and pooled, clocks warm
-    t = {"pool": [], "static": []}
+    other = "seeded" if a.seeded else "static"
+    other_run = (lambda: pool_run(True)) if a.seeded else static_run
+    pool_run(), other_run()   # untimed: sessions captured and pooled, clocks warm
+    t = {"pool": [], other: []}
     for _ in range(a.reps):
         t["pool"].append(pool_run())
-        t["static"].append(static_run())
+        t[other].append(other_run())
     res = {"tool": "bench_pool", "device": torch.cuda.get_device_name(0), "model": "tv2o-medium", "dtype": "bf16", "requests": n,
            "rows": a.rows, "prompt_lengths": [a.lmin, a.lmax], "events_to_generate": [a.gmin, a.gmax], "seed": a.seed,
            "capacity": capacity, "useful_events": useful, "static_parked_row_events": waste, "reps": a.reps}
@@ -122,8 +133,11 @@ def main():
                   "spread": round((max(secs) - min(secs)) / statistics.median(secs), 4),
                   "first_event_of_last_request_s": [round(x[1], 4) for x in v], "event_steps": v[0][2],
                   "prefill_groups": v[0][3], "ms_per_event_step": round(1e3 * statistics.median(secs) / v[0][2], 3)}
-    res["pool_over_static"] = round(statistics.median([x[0] for x in t["static"]]) / statistics.median([x[0] for x in t["pool"]]), 3)
-    res["ratio_predicted_from_parked_row_events"] = round((useful + waste) / useful, 3)
+    if a.seeded:
+        res["seeded_over_pool"] = round(statistics.median([x[0] for x in t["pool"]]) / statistics.median([x[0] for x in t["seeded"]]), 3)
+    else:
+        res["pool_over_static"] = round(statistics.median([x[0] for x in t["static"]]) / statistics.median([x[0] for x in t["pool"]]), 3)
+        res["ratio_predicted_from_parked_row_events"] = round((useful + waste) / useful, 3)
     line = json.dumps(res)
     print(line, flush=True)
     if a.out:

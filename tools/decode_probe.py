@@ -7,6 +7,8 @@
   2. the replay time of the session's graphs: net step at several cache lengths, token steps 0..7;
   3. aggregate throughput of G concurrent decode chains of 64/G sequences (threads x streams) -- what splitting the batch
      into independent chains buys when a chain is bound by dependent-launch latency.
+  4. (on request) the fused sampler, uniform against per-row, per instantiation;
+  5. (on request) the fused sampler, per-row against seeded, at each of the 8 token positions on the real grammar tables.
 """
 import os
 import sys
@@ -219,9 +221,55 @@ def section_4(B=64, V=3406, rounds=3):
         print(f"{inst} (ranges of {span} ids): " + ";  ".join(f"{k} " + " ".join(f"{x:.2f}" for x in v) for k, v in t.items()))
 
 
+def section_5(B=64, rounds=3):
+    """seeded (mh_sample_top_p_k_seeded: the variates computed by the top_k lanes) against per-row (mh_sample_top_p_k_rows: read from
+    q) at each of the 8 token positions on the real grammar tables -- every row a `note` event, so position 7 is the 2048-id
+    `duration` range; the instantiation follows the longest range of the position, as in the session"""
+    tok = mm.MIDITokenizerV2()
+    from midi_model_amd.tokenizer import grammar_tables
+    V, T = tok.vocab_size, tok.max_token_seq
+    print(f"== 5. fused sampler, per-row (mh_sample_top_p_k_rows) against seeded (mh_sample_top_p_k_seeded): us per launch, 48 launches "
+          f"in a replayed graph, B={B}, V={V}, bf16, top_k 20, runs alternating ==")
+    first, lo, hi, _ = grammar_tables(tok)
+    first = torch.tensor(first, dtype=torch.uint8)
+    lo_tab, hi_tab = torch.tensor(lo, dtype=torch.int32), torch.tensor(hi, dtype=torch.int32)
+    span, max_range = ops.mask_spans(first, lo_tab, hi_tab)
+    first, lo_tab, hi_tab = first.to(dev), lo_tab.to(dev), hi_tab.to(dev)
+    g = torch.Generator().manual_seed(0)
+    logits = (3.0 * torch.randn((B, V + (-V) % 8), generator=g)).to(dev, bf)
+    q = torch.empty((B, V)).exponential_(1.0, generator=g).to(dev)
+    out = torch.zeros((B,), dtype=torch.long, device=dev)
+    ev = torch.full((B,), tok.event_ids["note"], dtype=torch.long, device=dev)
+    ban = torch.zeros(V, dtype=torch.uint8, device=dev)
+    temp, top_p = torch.full((B,), 1.0, device=dev), torch.full((B,), 0.98, device=dev)
+    top_k = torch.full((B,), 20, dtype=torch.int32, device=dev)
+    seed = torch.arange(B, dtype=torch.int64, device=dev) * 1000003 + 12345
+    ctr = torch.arange(B, dtype=torch.int32, device=dev) + 17
+    for pos in range(T):
+        def rows():
+            for _ in range(48):
+                ops.sample_top_p_k_rows(logits, first, lo_tab, hi_tab, ev, pos, q, out, V, temp, top_p, top_k, ban, first_span=span,
+                                        max_range=max_range[pos])
+
+        def seeded():
+            for _ in range(48):
+                ops.sample_top_p_k_seeded(logits, first, lo_tab, hi_tab, ev, pos, seed, ctr, out, V, temp, top_p, top_k, ban,
+                                          first_span=span, max_range=max_range[pos])
+        t = {"rows": [], "seeded": []}
+        for _ in range(rounds):
+            for name, body in (("rows", rows), ("seeded", seeded)):
+                t[name].append(1e3 * graph_time(body) / 48)
+        r = span[1] - span[0] if pos == 0 else max_range[pos]
+        print(f"position {pos} (longest range {r} ids): " + ";  ".join(f"{k} " + " ".join(f"{x:.2f}" for x in v) for k, v in t.items()))
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     which = sys.argv[1:] or ["1", "2", "3"]
+    if "5" in which:
+        section_5()
+        if which == ["5"]:
+            sys.exit(0)
     if "4" in which:
         section_4()
         if which == ["4"]:
