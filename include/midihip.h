@@ -485,6 +485,17 @@ int mh_kv_store_seqs(const void* qkv, const int32_t* seq_start, void* kcache, vo
  * row id is outside [0, B), and a row at or past Lmax, instead of writing it.                                                */
 int mh_kv_store_seqs_rows(const void* qkv, const int32_t* seq_start, const int32_t* rows, void* kcache, void* vcache, int64_t n,
                           int64_t B, int64_t M, int H, int hd, int64_t Lmax, int dtype, void* stream);
+/* Fork cache sequences (DecodeSession.fork): kcache / vcache are a WHOLE cache tensor [layers, B, H, Lmax, hd] contiguous; src, dst
+ * and len are device int32 [n].  For pair p, positions [0, len[p]) of every (layer, head) of sequence src[p] are copied to the same
+ * place in sequence dst[p], K and V, every layer, in ONE launch; no other element of either cache is written.  Several pairs may
+ * name one source (the fan-out).  max_len is the host's bound on every len[p]: it sizes the grid, 1 <= max_len <= Lmax.  16 bytes
+ * per lane: hd % 8 == 0, bf16 or fp32.  The kernel drops a pair WHOLE, nothing written, when src[p] or dst[p] is outside [0, B) or
+ * src[p] == dst[p], and writes no position at or past min(len[p], Lmax); positions of a len[p] past max_len are simply not reached.
+ * The host refuses (MH_ERR_ARG, caches untouched) a null buffer by name, a bad dtype, hd % 8 != 0, n < 1, n > B, max_len outside
+ * [1, Lmax] and a grid past the launch limits (layers * H > 65535 or n > 65535).  The dst ids must be distinct and no id may stand
+ * on both sides (a chain 0 -> 1, 1 -> 2 has no defined order): the caller (midi_model_amd.ops.kv_fork_rows) checks its host copies. */
+int mh_kv_fork_rows(void* kcache, void* vcache, const int32_t* src, const int32_t* dst, const int32_t* len, int64_t n,
+                    int64_t max_len, int64_t layers, int64_t B, int H, int hd, int64_t Lmax, int dtype, void* stream);
 
 /* ---- grammar-masked softmax for the sampler (midi_model.py:202-223) -----------------------------------------
  * probs[b,:] = softmax(logits[b,:]/temp) * mask_b, mask_b = ids in [lo[b],hi[b]) or, when lo[b] < 0, the

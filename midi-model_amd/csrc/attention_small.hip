@@ -666,6 +666,57 @@ extern "C" int mh_kv_store_seqs_rows(const void* qkv, const int32_t* seq_start, 
   return MH_OK;
 }
 
+// Fork (DecodeSession.fork): positions [0, len[p]) of every (layer, head) of cache sequence src[p] are copied to the same place in
+// sequence dst[p], K and V, all layers in one launch; kc / vc are a whole KVState tensor [layers, B, H, Lmax, hd].  For a fixed
+// (layer, sequence, head) the run is len * hd contiguous elements: one lane per 16 bytes of it (blockIdx.x walks the run in chunks of
+// 256 lanes, blockIdx.y = layer * H + head, blockIdx.z = the pair), so a lane's two loads and two stores are the whole of its work and
+// nothing is divided.  A pair whose src or dst is outside [0, B), or whose src == dst, is dropped whole; a position at or past
+// min(len[p], Lmax) is not written.  The three tables are L2-resident ([n] int32 each) and read once per lane.
+template <typename T>
+__global__ __launch_bounds__(256) void kv_fork_rows_kernel(T* __restrict__ kc, T* __restrict__ vc, const int32_t* __restrict__ src,
+                                                           const int32_t* __restrict__ dst, const int32_t* __restrict__ len, int B,
+                                                           int H, int hd, int64_t Lmax) {
+  constexpr int N = Pack<T>::N;
+  const int p = blockIdx.z;
+  const int s = src[p], d = dst[p];
+  if (s < 0 || s >= B || d < 0 || d >= B || s == d) return;
+  int64_t L = len[p];
+  if (L > Lmax) L = Lmax;
+  const int64_t e = ((int64_t)blockIdx.x * 256 + threadIdx.x) * N;  // element of the run
+  if (e >= L * hd) return;
+  const int64_t layer = blockIdx.y / H, h = blockIdx.y % H;
+  const int64_t from = (((layer * B + s) * H + h) * Lmax) * hd + e;
+  const int64_t to = (((layer * B + d) * H + h) * Lmax) * hd + e;
+  // (kc and vc are read and written through the same pointer: src != dst, so the runs are disjoint)
+  st16(kc + to, ld16(kc + from));
+  st16(vc + to, ld16(vc + from));
+}
+
+// (the three tables live in device memory: the host refuses what it can see, the kernel drops the rest; ops.kv_fork_rows checks
+//  the host copies -- ids in range, dst distinct, no id on both sides, 1 <= len <= Lmax -- before the call)
+extern "C" int mh_kv_fork_rows(void* kcache, void* vcache, const int32_t* src, const int32_t* dst, const int32_t* len, int64_t n,
+                               int64_t max_len, int64_t layers, int64_t B, int H, int hd, int64_t Lmax, int dtype, void* stream) {
+  MH_REQUIRE(kcache != nullptr, "kv_fork_rows: kcache is NULL");
+  MH_REQUIRE(vcache != nullptr, "kv_fork_rows: vcache is NULL");
+  MH_REQUIRE(src != nullptr, "kv_fork_rows: src is NULL (one device int32 cache row per pair)");
+  MH_REQUIRE(dst != nullptr, "kv_fork_rows: dst is NULL (one device int32 cache row per pair)");
+  MH_REQUIRE(len != nullptr, "kv_fork_rows: len is NULL (one device int32 length per pair)");
+  MH_REQUIRE(dtype == MH_BF16 || dtype == MH_F32, "kv_fork_rows: bad dtype %d", dtype);
+  MH_REQUIRE(hd > 0 && hd % 8 == 0, "kv_fork_rows: head_dim %d is not a multiple of 8 (16 bytes per lane)", hd);
+  MH_REQUIRE(layers > 0 && B > 0 && B < (1 << 30) && H > 0 && Lmax > 0 && Lmax < (1ll << 31),
+             "kv_fork_rows: bad args layers=%ld B=%ld H=%d Lmax=%ld", (long)layers, (long)B, H, (long)Lmax);
+  MH_REQUIRE(n >= 1 && n <= B, "kv_fork_rows: %ld pairs for a cache of %ld sequences", (long)n, (long)B);
+  MH_REQUIRE(max_len >= 1 && max_len <= Lmax, "kv_fork_rows: max_len %ld outside [1, Lmax=%ld]", (long)max_len, (long)Lmax);
+  const int64_t per = 256 * (dtype == MH_BF16 ? 8 : 4);  // elements of a run that one workgroup covers
+  const int64_t gx = (max_len * hd + per - 1) / per, gy = layers * H;
+  MH_REQUIRE(gx < (1ll << 31) && gy <= 65535 && n <= 65535, "kv_fork_rows: a grid of %ld x %ld x %ld workgroups", (long)gx, (long)gy,
+             (long)n);
+  DISPATCH_T(dtype, (kv_fork_rows_kernel<T><<<dim3((unsigned)gx, (unsigned)gy, (unsigned)n), 256, 0, (hipStream_t)stream>>>(
+                        (T*)kcache, (T*)vcache, src, dst, len, (int)B, H, hd, Lmax)));
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
 // cache rows [0, n) of every (sequence, head) back into the K and V columns of rows [b * Stot, b * Stot + n) of a fused
 // qkv buffer [B * Stot, 3 H hd] (their q columns are zeroed: those query rows are never used); the inverse of kv_store_rows
 template <typename T>

@@ -67,6 +67,22 @@ Stale K/V at cache rows >= L of a reused row is never read: attention reads rows
 since the admission -- [0, L) by the prefill, row p by the net step that stood at p.  The noise graph runs on its own stream and
 touches ``q_all`` alone, the copy stream reads ``seq`` alone; an admission writes neither.  No graph is recaptured and no graph
 body changes: every buffer named above sits at the address the captures hold.
+
+``fork`` / ``hold`` (row_params sessions; pool.DecodePool drives them): a row is DUPLICATED into free rows between two events, without
+a second prefill.  ``fork(src, dst, lengths, ...)`` is one mh_kv_fork_rows launch over the whole of ``kv1`` (every layer, K and V, rows
+[0, lengths[p]) of sequence src[p] into sequence dst[p]) and the scatter of an admission with ``hidden[dst] = hidden[src]`` and
+``pos[dst] = lengths``; it runs no forward.  The same stream order carries it:
+  1. the net step over the source's last event runs first, on the session's stream: it wrote the source's K/V row lengths[p] - 1 and
+     its ``hidden``, and advanced its ``pos`` to lengths[p] -- so the source's cache rows [0, lengths[p]) and ``hidden`` are exactly
+     the state from which event lengths[p] is sampled;
+  2. the fork follows ON THE SAME STREAM: the copy reads that state and overwrites cache rows [0, lengths[p]), ``hidden``, ``pos`` and
+     the settings of the destination rows -- free rows, whose own state nothing reads; the source rows are only read;
+  3. the next token steps, on the same stream again, sample the destination rows from the copied ``hidden``; the net step behind them
+     appends at row lengths[p] of each sequence on its own.
+Stale K/V at cache rows >= lengths[p] of a destination is never read, by the argument above.  A source that has reached its max_len is
+PARKED: the net steps that follow keep writing its cache row max_len and its ``hidden``, never rows [0, max_len).  ``hold(rows)``
+therefore copies ``hidden[rows]`` into ``held_hidden`` right behind the net step over the row's last event, and a later
+``fork(from_held=...)`` takes ``hidden`` from there: a held row can be continued any number of steps later.
 """
 from __future__ import annotations
 
@@ -177,6 +193,8 @@ class DecodeSession:
         self.gen = torch.Generator(device=dev) if self.use_graphs and not self.seeded else None
         self._user_gen = None
         self._admit_stage = None   # the pinned host block of the last admission (admit)
+        self._fork_stage = None    # ... and of the last fork
+        self.held_hidden = None    # [B, D]: hidden rows kept by hold(), allocated at first use
         self._pool = None
         self._off = 0          # philox offset of the next draw the reference loop would make
         self._draw_inc = 0     # philox offset consumed by one [B, V] exponential_ call
@@ -531,25 +549,9 @@ class DecodeSession:
                     (np.uint8, first_masks.numpy().reshape(-1)), (np.uint8, bans.numpy().reshape(-1))]
         if self.seeded:
             sections.append((np.int64, seed_vals))
-        parts, offs, at = [], [], 0
-        for ty, v in sections:
-            a = np.ascontiguousarray(np.asarray(v, dtype=ty)).view(np.uint8)
-            parts.append(a)
-            offs.append((at, a.size))
-            at += (a.size + 15) // 16 * 16
-        host = np.zeros(at, dtype=np.uint8)
-        for a, (o, sz) in zip(parts, offs):
-            host[o:o + sz] = a
         dev = m.device
-        block = torch.from_numpy(host)
-        if dev.type == "cuda":  # pinned staging, non-blocking (as SeqPlan.upload); kept alive until the next admission
-            self._admit_stage = block.pin_memory()
-            block = self._admit_stage.to(dev, non_blocking=True)
-        tys = (torch.int64, torch.int64, torch.int32, torch.int32, torch.int32, torch.int32, torch.float32, torch.float32,
-               torch.uint8, torch.uint8)
-        idx, last, rows_dev, len_dev, lim_dev, k_dev, t_dev, p_dev, first_dev, ban_dev = \
-            (block[o:o + sz].view(ty) for ty, (o, sz) in zip(tys, offs))
-        seed_dev = block[offs[10][0]:offs[10][0] + offs[10][1]].view(torch.int64) if self.seeded else None
+        idx, last, rows_dev, len_dev, lim_dev, k_dev, t_dev, p_dev, first_dev, ban_dev, *seed_dev = \
+            self._stage_block(sections, "_admit_stage")
         # ---- one packed forward over the admitted prompts alone, K/V into the chosen cache rows
         plan = ops.attn_seq_plan(lengths, spec.H).upload(dev)
         e = torch.empty((M, spec.D), dtype=m.dtype, device=dev)
@@ -566,7 +568,110 @@ class DecodeSession:
         self.first_mask.index_copy_(0, idx, first_dev.view(n, V))
         self.ban.index_copy_(0, idx, ban_dev.view(n, V))
         if self.seeded:
-            self.seed_rows.index_copy_(0, idx, seed_dev)
+            self.seed_rows.index_copy_(0, idx, seed_dev[0])
+
+    _STAGE_TYPES = {np.int64: torch.int64, np.int32: torch.int32, np.float32: torch.float32, np.uint8: torch.uint8}
+
+    def _stage_block(self, sections, slot: str) -> list:
+        """(admit, fork) ``sections`` [(numpy type, values)] laid into ONE host block, every section on a multiple of 16 bytes, and
+        uploaded once; -> the sections as typed views of the device copy.  On a GPU the block is pinned and the copy non-blocking
+        (as SeqPlan.upload); the pinned block is kept alive under ``slot`` until the next call that names it."""
+        parts, offs, at = [], [], 0
+        for ty, v in sections:
+            a = np.ascontiguousarray(np.asarray(v, dtype=ty)).view(np.uint8)
+            parts.append(a)
+            offs.append((at, a.size))
+            at += (a.size + 15) // 16 * 16
+        host = np.zeros(at, dtype=np.uint8)
+        for a, (o, sz) in zip(parts, offs):
+            host[o:o + sz] = a
+        block = torch.from_numpy(host)
+        if self.model.device.type == "cuda":
+            setattr(self, slot, block.pin_memory())
+            block = getattr(self, slot).to(self.model.device, non_blocking=True)
+        return [block[o:o + sz].view(self._STAGE_TYPES[ty]) for (ty, _), (o, sz) in zip(sections, offs)]
+
+    def fork(self, src_rows, dst_rows, lengths, limits, temp, top_p, top_k, first_masks, bans, seeds=None, from_held=None) -> None:
+        """(row_params) n rows of the running batch become continuations of other rows, between two events, WITHOUT a forward (the
+        header has the stream-order argument).  For pair p: cache rows [0, lengths[p]) of every layer of sequence src_rows[p] are
+        copied to sequence dst_rows[p] -- ONE mh_kv_fork_rows launch over the whole of ``kv1`` -- and row dst_rows[p] takes
+        hidden[src_rows[p]] (``from_held[p]`` set: held_hidden[src_rows[p]], what ``hold`` kept), pos = lengths[p], pos_limit =
+        limits[p], and the sampler arrays, both masks and, in a seeded session, the seed from the arguments (as ``admit`` takes
+        them).  lengths[p] is the number of events whose K/V the source row holds: the caller's to know -- the session keeps no
+        host copy of ``pos``.  Several pairs may name one source; the dst rows are distinct and no row stands on both sides.
+        The per-row values travel in ONE pinned host block and are scattered by index_copy_ calls, as in ``admit``.  No forward,
+        no capture, no recapture: every buffer sits at the address the graphs hold.  ``ValueError`` before any launch."""
+        if not (self.ragged and self.row_params):
+            raise ValueError("DecodeSession.fork: rows are forked in a ragged=True, row_params=True session only")
+        from .ops_fork import check_pairs
+        V = self.V
+        limits = [int(n) for n in limits]
+        src, dst, lengths = check_pairs(src_rows, dst_rows, lengths, self.B, self.cap)
+        n = len(src)
+        vals = [list(np.asarray(x).reshape(-1).tolist()) for x in (temp, top_p, top_k)]
+        first_masks, bans = torch.as_tensor(first_masks), torch.as_tensor(bans)
+        if len(limits) != n or any(len(v) != n for v in vals):
+            raise ValueError(f"fork: {n} pairs, {len(limits)} limits, {[len(v) for v in vals]} sampler values")
+        if any(L > lim or lim + 1 > self.cap for L, lim in zip(lengths, limits)):
+            raise ValueError(f"fork: rows of {lengths} events, limits {limits}, in a session of capacity {self.cap} (a row may not "
+                             f"exceed its limit, and limit + 1 rows are needed)")
+        kmax = min(ops.SAMPLE_MAX_K, V)
+        if any(int(k) != k or not 1 <= k <= kmax for k in vals[2]):
+            raise ValueError(f"fork: top_k {vals[2]} outside [1, {kmax}]")
+        for name, t in (("first_masks", first_masks), ("bans", bans)):
+            if t.dtype != torch.uint8 or t.shape != (n, V) or t.device.type != "cpu":
+                raise ValueError(f"fork: {name} must be a host uint8 tensor [{n}, {V}]: {t.dtype} {tuple(t.shape)} on {t.device}")
+        if self.seeded:
+            seed_vals = self._seed_values(seeds, n, "fork")
+        elif seeds is not None:
+            raise ValueError("fork: seeds are taken by a seeded=True session only")
+        held = [bool(x) for x in from_held] if from_held is not None else [False] * n
+        if len(held) != n:
+            raise ValueError(f"fork: from_held holds {len(held)} values for {n} pairs")
+        if any(held) and self.held_hidden is None:
+            raise ValueError("fork: from_held names a row, and hold() has kept none")
+        # ---- the one host block: [dst i64 | src i64 | src, dst, lengths i32 [3, n] | limits i32 | top_k i32 | temp f32 | top_p f32 |
+        #      first u8 | ban u8 | held u8 (| seeds i64)]
+        sections = [(np.int64, dst), (np.int64, src), (np.int32, src + dst + lengths), (np.int32, limits), (np.int32, vals[2]),
+                    (np.float32, vals[0]), (np.float32, vals[1]), (np.uint8, first_masks.numpy().reshape(-1)),
+                    (np.uint8, bans.numpy().reshape(-1)), (np.uint8, held)]
+        if self.seeded:
+            sections.append((np.int64, seed_vals))
+        idx, from_idx, pairs, lim_dev, k_dev, t_dev, p_dev, first_dev, ban_dev, held_dev, *seed_dev = \
+            self._stage_block(sections, "_fork_stage")
+        pairs = pairs.view(3, n)
+        # ---- the K/V of every layer, one launch
+        ops.kv_fork_rows(self.kv1.k, self.kv1.v, src, dst, lengths, dev=pairs)
+        # ---- the rows' state
+        h = self.hidden.index_select(0, from_idx)
+        if any(held):
+            h = torch.where(held_dev.bool()[:, None], self.held_hidden.index_select(0, from_idx), h)
+        self.hidden.index_copy_(0, idx, h)
+        self.pos.index_copy_(0, idx, pairs[2])
+        self.pos_limit.index_copy_(0, idx, lim_dev)
+        self.temp_rows.index_copy_(0, idx, t_dev)
+        self.top_p_rows.index_copy_(0, idx, p_dev)
+        self.top_k_rows.index_copy_(0, idx, k_dev)
+        self.first_mask.index_copy_(0, idx, first_dev.view(n, V))
+        self.ban.index_copy_(0, idx, ban_dev.view(n, V))
+        if self.seeded:
+            self.seed_rows.index_copy_(0, idx, seed_dev[0])
+
+    def hold(self, rows) -> None:
+        """(row_params) keep ``hidden[rows]`` -- the net output over those rows' LAST event -- in ``held_hidden`` [B, D] (allocated
+        at first use) at the same row indices.  A parked row keeps being sampled and the next net step overwrites its ``hidden``;
+        its K/V rows [0, max_len) stay as they are (a parked row writes cache row max_len alone), so the copy is all that a later
+        ``fork(..., from_held=...)`` needs to continue the row.  Call it behind the net step over the row's last event."""
+        if not (self.ragged and self.row_params):
+            raise ValueError("DecodeSession.hold: rows are held on a ragged=True, row_params=True session only")
+        from .ops_pool import check_rows
+        ids = check_rows(rows, len(rows), self.B)
+        if not ids:
+            return
+        if self.held_hidden is None:
+            self.held_hidden = torch.zeros_like(self.hidden)
+        idx = torch.tensor(ids, dtype=torch.int64).to(self.model.device)
+        self.held_hidden.index_copy_(0, idx, self.hidden.index_select(0, idx))
 
     def release(self, rows) -> None:
         """(row_params) rows whose requests have finished: pos = pos_limit = 0 there.  A free row is still embedded, attended and

@@ -613,9 +613,14 @@ _ROWS = ("sample_top_p_k_rows",)
 _POOL = ("kv_store_seqs_rows",)
 # ... and the sampler with a seed per row, with its generator on its own (ops_seeded.py; stand-ins in tests/emu_seeded.py)
 _SEEDED = ("sample_top_p_k_seeded", "sample_noise_seeded")
+# ... and the copy of cache sequences inside a live cache, a fork (ops_fork.py; stand-in in tests/emu_fork.py)
+_FORK = ("kv_fork_rows",)
 
 
 def __getattr__(name: str):
+    if name in _FORK:
+        from . import ops_fork
+        return getattr(ops_fork, name)
     if name in _SEEDED:
         from . import ops_seeded
         return getattr(ops_seeded, name)

@@ -39,9 +39,33 @@ before.  The stated limits of that promise:
 Every request of a seeded pool needs a seed, an unseeded pool refuses one, and ``generator`` with ``seeded=True`` is refused.  Free
 and parked rows keep being sampled and dropped; their seeds are whatever the row last held.  Measured: DESIGN 7.8.
 
+FORKS.  A row can be DUPLICATED into free rows without a second prefill: its K/V rows [0, L) of every layer are
+copied by one kernel launch (``mh_kv_fork_rows``) and its ``hidden`` row, position and a new set of per-row values are scattered as
+an admission scatters them (``DecodeSession.fork``).  Three entry points share that:
+  * ``submit(prompt, ..., n=k)`` -> k ids, SIBLINGS on one prompt and one set of settings (a seeded pool: k seeds).  The group is
+    admitted whole -- it waits at the head of the FIFO until k rows are free -- its leader is prefilled in the admission's one packed
+    forward, the other k - 1 rows are filled by one fork right behind it.  One prompt's prefill instead of k.
+  * ``submit(..., hold=True)``: a request that finishes by reaching ``max_len`` KEEPS its row (``held()`` lists such requests,
+    ``drop(rid)`` releases the row; they do not count in ``pending()``).  ``step()`` then runs the net step over the request's final
+    event as well -- without ``hold`` it is skipped when nothing continues -- and ``DecodeSession.hold`` keeps the row's ``hidden``:
+    the parked row keeps being sampled and net-stepped with the batch, which overwrites ``hidden`` and cache row ``max_len``, never
+    cache rows [0, max_len).  A held request that ends on EOS is released as usual.
+  * ``fork(rid, count, max_len=..., seed=...)`` -> ``count`` new requests that continue a running or held request from where it
+    stands, in the lowest free rows, taken at once and ahead of the queue; their first event comes with the next ``step()``, and
+    ``result()`` of a child has the inherited events in front.
+In a seeded pool the variate counter is ``pos``, the index of the event in the result, and a child continues its parent's counter
+under its own seed: a child given the parent's seed and settings repeats the parent, and a held request forked under its own seed
+with a larger ``max_len`` gives exactly what an uninterrupted request with that ``max_len`` gives -- at equal launch shapes, the
+limit stated above.  ``n == 1`` without ``hold`` runs exactly what it ran.  Measured (one MI355X, ``profiles/fork_ab.txt``, DESIGN
+7.9; ``tools/bench_fork.py``, tv2o-medium bf16, 64 rows): admitting ``n=4`` siblings against four ``submit``s of the prompt, the
+admitting step takes 5.58 against 10.75 ms at 4000 prompt events, 4.29 against 6.46 ms at 2048, and 3.50 against 3.32 ms at 64 (no
+gain: a short admission is its launches); the copy kernel alone runs at 0.85 to 0.97 of the chip's copy rate at those lengths.
+
 Out of scope:
   * a background thread or server loop -- the caller owns the loop (and the thread: one pool, one thread);
-  * ``share_prompt`` inside the pool;
+  * the shared-prefix ATTENTION of ``generate(share_prompt=True)`` inside the pool: siblings and children share a prompt's prefill,
+    not its K/V -- every row owns a copy and reads it in full at every event;
+  * a held row's K/V outliving its pool, or moving to another pool: ``close()`` ends every hold;
   * chunking a long admission: a 4096-event prefill on tv2o-medium is 4096 x 0.4 GFLOP of projections (12 layers x 16.8 M
     weights x 2) plus ~0.8 TFLOP of causal attention, about 2.5 TFLOP -- 2.5 to 5 ms at the 500 to 1000 TFLOP/s the block
     forward runs at, i.e. about one or two decoded events -- arithmetic, not a measurement;
@@ -65,14 +89,20 @@ import numpy as np
 import torch
 
 
-class _Request:
-    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done")  # (rp["seed"]: a seeded pool's request)
+_SETTINGS = ("max_len", "temp", "top_p", "top_k", "ban_eos", "disable_patch_change", "disable_control_change", "disable_channels")
 
-    def __init__(self, prompt: np.ndarray, rp: dict):
-        self.prompt, self.rp, self.max_len = prompt, rp, rp["max_len"][0]
+
+class _Request:
+    # (rp["seed"]: a seeded pool's request; prompt: a child's holds its parent's result at the fork; group: the size of the sibling
+    #  group this request LEADS in the queue, 0 for the siblings behind it; kw: the settings as given, a child's defaults)
+    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done", "hold", "held", "eos", "group", "kw")
+
+    def __init__(self, prompt: np.ndarray, rp: dict, kw: dict, hold: bool = False, group: int = 1):
+        self.prompt, self.rp, self.max_len, self.kw = prompt, rp, rp["max_len"][0], kw
         self.events: List[np.ndarray] = []
         self.row: Optional[int] = None
         self.done = False
+        self.hold, self.held, self.eos, self.group = bool(hold), False, False, group
 
 
 class DecodePool:
@@ -88,38 +118,136 @@ class DecodePool:
         self.ses = None                                  # taken from the model's pool at the first admission
         self.free: List[int] = list(range(self.rows))    # ascending: the lowest free row is taken first
         self.queue: deque = deque()                      # request ids, FIFO
-        self.occupied: Dict[int, int] = {}               # row -> request id
+        self.occupied: Dict[int, int] = {}               # row -> request id (running)
+        self.held_rows: Dict[int, int] = {}              # row -> request id (finished at max_len with hold=True: the row is kept)
         self.requests: Dict[int, _Request] = {}
         self._next_id = 0
         self._closed = False
 
     # ---- the caller's side ----------------------------------------------------------------------------------------------
     def submit(self, prompt, max_len=512, temp=1.0, top_p=0.98, top_k=20, ban_eos=False, disable_patch_change=False,
-               disable_control_change=False, disable_channels=None, seed=None) -> int:
+               disable_control_change=False, disable_channels=None, seed=None, n=1, hold=False):
         """queue one request; -> its id.  Checked as ``generate_ragged`` checks a row with values of its own (the same code, the
         same ``ValueError``s), plus ``max_len + 1 > capacity``; the prompt is cropped to its last 4096 events, as the stream forms
-        crop.  ``seed``: required in a seeded pool (an int in [0, 2^64)), refused in an unseeded one.  Nothing is launched here."""
+        crop.  ``seed``: required in a seeded pool (an int in [0, 2^64)), refused in an unseeded one.  Nothing is launched here.
+        ``n`` > 1 (an int in [1, rows]): n SIBLINGS, continuations of the one prompt that share every setting; -> the list of their n
+        ids.  In a seeded pool ``seed`` is then a sequence of n ints.  The group is admitted whole -- it waits at the head of the
+        queue until n rows are free, and later requests wait behind it; its leader is prefilled in the admission's one packed
+        forward, the other n - 1 rows are filled by one ``DecodeSession.fork`` right behind it: one prefill and one K/V copy per
+        sibling instead of n prefills.  ``n == 1`` runs exactly what it ran, and its id is a plain int.
+        ``hold``: when the request finishes by reaching ``max_len`` its row is kept (``held()``, ``fork()``, ``drop()``); one that
+        ends on EOS is released as usual."""
         if self._closed:
             raise ValueError("DecodePool.submit: the pool is closed")
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= self.rows:
+            raise ValueError(f"DecodePool.submit: n = {n!r} is not an integer in [1, {self.rows}] (the pool's rows)")
+        n = int(n)
+        seeds = self._seeds(seed, n, "submit", "n")
+        kw = dict(zip(_SETTINGS, (max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change,
+                                  disable_channels)))
+        checked = [self._checked(prompt, kw, s, "submit") for s in seeds]
+        rids = []
+        for i, (p, rp) in enumerate(checked):
+            rids.append(self._next_id)
+            self._next_id += 1
+            self.requests[rids[-1]] = _Request(p, rp, kw, hold=hold, group=n if i == 0 else 0)
+            self.queue.append(rids[-1])
+        return rids[0] if n == 1 else rids
+
+    def _seeds(self, seed, n: int, what: str, count_name: str) -> list:
+        """the seed argument of submit(n=) / fork(count=) -> n seeds (None each in an unseeded pool); one request takes a scalar,
+        several take a sequence of that many (each is checked as one seed is, by _check_request)"""
         if self.seeded and seed is None:
-            raise ValueError("DecodePool.submit: every request of a seeded pool needs a seed (an integer in [0, 2^64))")
+            raise ValueError(f"DecodePool.{what}: every request of a seeded pool needs a seed (an integer in [0, 2^64))")
         if not self.seeded and seed is not None:
-            raise ValueError("DecodePool.submit: this pool shares one noise stream among its rows; a seed per request needs "
+            raise ValueError(f"DecodePool.{what}: this pool shares one noise stream among its rows; a seed per request needs "
                              "decode_pool(..., seeded=True)")
-        p, rp = self.model._check_request(prompt, max_len, temp, top_p, top_k, ban_eos, disable_patch_change,
-                                          disable_control_change, disable_channels, seed=seed)
+        if seed is None or n == 1:
+            return [seed] * n
+        per_row = self.model._per_row(seed)
+        if not per_row or len(seed) != n:
+            raise ValueError(f"DecodePool.{what}: {count_name} = {n} takes a sequence of {n} seeds, one per request"
+                             + (f": it holds {len(seed)}" if per_row else f", not the scalar {seed!r}"))
+        return seed.tolist() if isinstance(seed, (np.ndarray, torch.Tensor)) else list(seed)
+
+    def _checked(self, prompt, kw: dict, seed, what: str, crop=4096):
+        """_check_request on the settings ``kw`` + the pool's capacity rule -> (prompt, the one-row dict)"""
+        p, rp = self.model._check_request(prompt, *(kw[name] for name in _SETTINGS), crop=crop, seed=seed)
         if rp["max_len"][0] + 1 > self.capacity:
-            raise ValueError(f"DecodePool.submit: max_len {rp['max_len'][0]} in a pool of capacity {self.capacity} (max_len + 1 "
+            raise ValueError(f"DecodePool.{what}: max_len {rp['max_len'][0]} in a pool of capacity {self.capacity} (max_len + 1 "
                              f"rows are needed)")
-        rid = self._next_id
-        self._next_id += 1
-        self.requests[rid] = _Request(p, rp)
-        self.queue.append(rid)
-        return rid
+        return p, rp
 
     def pending(self) -> int:
-        """requests queued or running"""
+        """requests queued or running (a held request is neither)"""
         return len(self.queue) + len(self.occupied)
+
+    def held(self) -> List[int]:
+        """ids of the requests that finished with ``hold=True`` and still keep their row"""
+        return sorted(self.held_rows.values())
+
+    def drop(self, rid: int) -> None:
+        """release the row of held request ``rid`` (its result stays)"""
+        r = self.requests.get(rid)
+        if self._closed or r is None or not r.held:
+            raise ValueError(f"DecodePool.drop: request {rid!r} holds no row of this pool")
+        with torch.inference_mode():
+            self.ses.release([r.row])
+        del self.held_rows[r.row]
+        self.free = sorted(self.free + [r.row])
+        r.row, r.held = None, False
+
+    def fork(self, rid: int, count: int = 1, max_len=None, temp=None, top_p=None, top_k=None, ban_eos=None,
+             disable_patch_change=None, disable_control_change=None, disable_channels=None, seed=None, hold=False) -> List[int]:
+        """``count`` new requests that CONTINUE request ``rid`` from where it stands: their prompt is ``result(rid)`` as it is now
+        (inherited events in front of their own in ``result()``), their first event is reported by the next ``step()``; -> their
+        ids.  The parent is running or held (``submit(hold=True)``); it runs on, or stays held, untouched.  No prefill: the
+        parent's K/V is copied into ``count`` free rows and the rows' state set in one ``DecodeSession.fork`` -- one kernel launch
+        and the scatter of an admission.  The rows are taken NOW, the lowest first and ahead of the queue.  A setting left at None
+        is the parent's; ``max_len`` must exceed ``len(result(rid))`` (so a held parent's children need one).  In a seeded pool
+        ``seed`` is an int for one child, a sequence of ``count`` ints for several.
+        Seeded pools: the variate counter of an event is its index in the result, so a child continues the parent's counter under
+        its own seed -- a child given the parent's seed and settings repeats the parent event for event, and a held request forked
+        under its own seed with a larger ``max_len`` gives exactly what an uninterrupted request with that ``max_len`` gives.  The
+        limit is the module docstring's: equal launch shapes (the same pool size; the parent's prefill in the same admission
+        grouping) -- the copy itself is bit-exact and the decode kernels treat rows independently.
+        ``ValueError`` before any launch: an unknown, queued, released or EOS-ended parent, fewer than ``count`` free rows,
+        ``max_len <= len(result(rid))``, ``max_len + 1 > capacity``, and every refusal of ``submit``'s settings."""
+        if self._closed:
+            raise ValueError("DecodePool.fork: the pool is closed")
+        r = self.requests.get(rid) if isinstance(rid, (int, np.integer)) and not isinstance(rid, bool) else None
+        if r is None:
+            raise ValueError(f"DecodePool.fork: no request {rid!r}")
+        if r.eos:
+            raise ValueError(f"DecodePool.fork: request {rid} ended on EOS: there is nothing to continue")
+        if r.row is None:
+            raise ValueError(f"DecodePool.fork: request {rid} is {'released: its row is gone' if r.done else 'still queued'} -- a "
+                             f"parent is running, or held (submit(hold=True))")
+        if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or not 1 <= count <= self.rows:
+            raise ValueError(f"DecodePool.fork: count = {count!r} is not an integer in [1, {self.rows}] (the pool's rows)")
+        count = int(count)
+        if count > len(self.free):
+            raise ValueError(f"DecodePool.fork: {count} rows are needed, {len(self.free)} are free")
+        seeds = self._seeds(seed, count, "fork", "count")
+        given = (max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change, disable_channels)
+        kw = {name: r.kw[name] if v is None else v for name, v in zip(_SETTINGS, given)}
+        prompt = self.result(rid)
+        checked = [self._checked(prompt, kw, s, "fork", crop=None) for s in seeds]
+        rows = self.free[:count]
+        rp = {name: [c[1][name][0] for c in checked] for name in checked[0][1]}
+        first, ban = self.model._mask_rows(rp)
+        with torch.inference_mode():
+            self.ses.fork([r.row] * count, rows, [len(prompt)] * count, rp["max_len"], rp["temp"], rp["top_p"], rp["top_k"],
+                          first, ban, seeds=rp.get("seed"), from_held=[r.held] * count)
+        del self.free[:count]
+        rids = []
+        for row, (p, one) in zip(rows, checked):
+            rids.append(self._next_id)
+            self._next_id += 1
+            child = self.requests[rids[-1]] = _Request(p, one, kw, hold=hold)
+            child.row = row
+            self.occupied[row] = rids[-1]
+        return rids
 
     def result(self, rid: int, forget: bool = False) -> np.ndarray:
         """request ``rid``'s events so far, ``(<= max_len, 8) int64`` with its (cropped, padded) prompt in front; ``forget``: drop a
@@ -164,12 +292,24 @@ class DecodePool:
         return self.ses
 
     def _admit_queued(self) -> None:
-        k = min(len(self.free), len(self.queue))
+        # FIFO, whole sibling groups: the request at the head leads a group of r.group rows (1: a lone request); a group that
+        # does not fit waits there, and what is queued behind it waits with it
+        groups, k = [], 0
+        while self.queue and k + self.requests[self.queue[0]].group <= len(self.free):
+            g = self.requests[self.queue[0]].group
+            groups.append([self.queue.popleft() for _ in range(g)])
+            k += g
         if k == 0:
             return
-        rows, rids = self.free[:k], [self.queue.popleft() for _ in range(k)]
-        reqs = [self.requests[rid] for rid in rids]
+        taken = self.free[:k]
         del self.free[:k]
+        rows, rids, forks, at = [], [], [], 0   # the leaders and their rows; (leader's row, sibling's row, sibling's id)
+        for grp in groups:
+            rows.append(taken[at])
+            rids.append(grp[0])
+            forks += [(taken[at], taken[at + i], rid) for i, rid in enumerate(grp) if i > 0]
+            at += len(grp)
+        reqs = [self.requests[rid] for rid in rids]
         rp = {name: [r.rp[name][0] for r in reqs] for name in reqs[0].rp}
         first, ban = self.model._mask_rows(rp)
         tokens = torch.from_numpy(np.concatenate([r.prompt for r in reqs], axis=0))
@@ -178,6 +318,15 @@ class DecodePool:
         for row, rid, r in zip(rows, rids, reqs):
             r.row = row
             self.occupied[row] = rid
+        if forks:  # the siblings: the leaders' K/V and last hidden rows, right behind the prefill that made them
+            sibs = [self.requests[rid] for _, _, rid in forks]
+            rp = {name: [r.rp[name][0] for r in sibs] for name in sibs[0].rp}
+            first, ban = self.model._mask_rows(rp)
+            self.ses.fork([s for s, _, _ in forks], [d for _, d, _ in forks], [len(r.prompt) for r in sibs], rp["max_len"],
+                          rp["temp"], rp["top_p"], rp["top_k"], first, ban, seeds=rp.get("seed"))
+            for (_, row, rid), r in zip(forks, sibs):
+                r.row = row
+                self.occupied[row] = rid
 
     def step(self) -> List[Tuple[int, np.ndarray, bool]]:
         """admit what fits, sample one event for every row, -> [(request id, event np.int64 (8,), done)] for the occupied rows,
@@ -190,25 +339,37 @@ class DecodePool:
         eos = self.model.tokenizer.eos_id
         with torch.inference_mode():
             self._admit_queued()
+            if not self.occupied:  # (a sibling group at the head of the queue, and held requests on the rows it waits for)
+                raise RuntimeError(f"DecodePool.step: nothing runs and the group of {self.requests[self.queue[0]].group} requests "
+                                   f"at the head of the queue cannot be admitted: {len(self.free)} rows are free, "
+                                   f"{len(self.held_rows)} held -- drop() a held request")
             ses = self.ses
             live = [row in self.occupied for row in range(self.rows)]
             running = [self.requests[rid] for rid in self.occupied.values()]
-            more = any(len(r.prompt) + len(r.events) + 1 < r.max_len for r in running)
+            # (a request that is to be held needs the net step over its LAST event too: its K/V row max_len - 1 and the hidden row
+            #  that hold() keeps)
+            more = any(len(r.prompt) + len(r.events) + 1 < r.max_len or r.hold for r in running)
             speculative = more and ses.g_steps is not None and _SPECULATIVE_NET
             event, _ = ses.sample_event(then_net=speculative, live=live)
-            out, finished = [], []
+            out, finished, keep = [], [], []
             for row, rid in sorted(self.occupied.items(), key=lambda kv: kv[1]):
                 r = self.requests[rid]
                 ev = event[row].copy()
                 r.events.append(ev)
-                r.done = bool(ev[0] == eos) or len(r.prompt) + len(r.events) >= r.max_len
+                r.eos = bool(ev[0] == eos)
+                r.done = r.eos or len(r.prompt) + len(r.events) >= r.max_len
                 if r.done:
-                    finished.append(row)
+                    (keep if r.hold and not r.eos else finished).append(row)
                 out.append((rid, ev, r.done))
-            if len(finished) < len(out):  # a request continues: the next event's draws, under the net step over this event
+            if len(finished) + len(keep) < len(out):  # a request continues: the next event's draws, under the net step over this event
                 ses.draw_noise()
-                if not speculative:
-                    ses.net_step()
+            if (len(finished) < len(out)) and not speculative:  # ... or is to be held
+                ses.net_step()
+            if keep:  # (behind the net step over their last event: the rows stay parked at max_len, nothing is released)
+                ses.hold(keep)
+                for row in keep:
+                    rid = self.held_rows[row] = self.occupied.pop(row)
+                    self.requests[rid].held = True
             if finished:  # (behind the net step, which advanced these rows with the rest)
                 ses.release(finished)
                 for row in finished:
