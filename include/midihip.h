@@ -456,6 +456,28 @@ int mh_attn_decode_append_shared(const void* qkv, const float* cos_t, const floa
                                  const float* ws, int64_t ws_floats, void* o, int64_t B, int H, int hd, int64_t Lsuf,
                                  int64_t Pmax, int64_t pre_len, int64_t pos, float scale, const int32_t* pre_len_dev,
                                  const int32_t* pos_dev, int dtype, void* stream);
+/* The same two launches for a batch whose rows stand at positions of their own behind G prompts (DecodeSession(prefix_slots=G),
+ * the decode pool): kpre / vpre [G, H, Pmax, hd] are G prefix SLOTS, slot_len a device int32 [G] (0: the slot is empty; clamped
+ * to Pmax), row_slot a device int32 [B] (the slot whose prompt row b continues; -1 or any value outside [0, G): none), row_pos a
+ * device int32 [B] (row b's ABSOLUTE position).  With pre_b = slot_len[row_slot[b]], or 0 for a row without a slot, cache row j
+ * of ksuf / vsuf [B, H, Lsuf, hd] holds absolute position pre_b + j.  All three arrays are always read on the device.
+ *   mh_attn_prefix_partial_slots: grid (head x chunk, slot).  A workgroup returns at once when its chunk lies past slot_len[g]
+ *     or when no row names slot g; otherwise it reads the chunk's K/V once and runs it against the member rows of slot g in
+ *     ascending row order (found inside the kernel from row_slot), each rotated at its own row_pos[b], and writes the partial
+ *     of (b, h, chunk) where mh_attn_prefix_partial writes it.  Per row the arithmetic is that kernel's, bit for bit.  Partials
+ *     of rows without a slot and of chunks at or past ceil(slot_len / chunk) are not written.  B <= 4096, G <= 65535.
+ *   mh_attn_decode_append_rows_shared: RoPE at row_pos[b], the new k and v rows to cache row row_pos[b] - pre_b, attention over
+ *     cache rows [0, row_pos[b] - pre_b], then the merge of the row's ceil(pre_b / chunk) partials in chunk order.  A row with
+ *     pre_b == 0 merges none and does the arithmetic of mh_attn_decode_append_rows.
+ * bf16 and fp32, hd == 64 only; anything else, a NULL array or a short workspace is MH_ERR_ARG before any launch.           */
+int mh_attn_prefix_partial_slots(const void* qkv, const float* cos_t, const float* sin_t, const void* kpre, const void* vpre,
+                                 const int32_t* slot_len, const int32_t* row_slot, const int32_t* row_pos, float* ws,
+                                 int64_t ws_floats, int64_t B, int H, int hd, int64_t G, int64_t Pmax, float scale, int dtype,
+                                 void* stream);
+int mh_attn_decode_append_rows_shared(const void* qkv, const float* cos_t, const float* sin_t, void* ksuf, void* vsuf,
+                                      const float* ws, int64_t ws_floats, void* o, int64_t B, int H, int hd, int64_t Lsuf,
+                                      int64_t G, int64_t Pmax, float scale, const int32_t* slot_len, const int32_t* row_slot,
+                                      const int32_t* row_pos, int dtype, void* stream);
 /* A chunk of q_len > 1 new positions behind n cached ones (a cache-carrying forward, midi_model.py:137-150 with a non-empty
  * DynamicCache; TF:integrations/sdpa_attention.py:79-166): mh_kv_store_rows appends the chunk's rotated K and V at cache rows
  * [pos0, pos0 + S); mh_kv_gather_rows copies cache rows [0, n) into the K and V columns of rows [b*Stot, b*Stot + n) of a fused

@@ -22,6 +22,17 @@
 // against them from registers.  The four waves' states meet in LDS and leave as one partial.  P is rounded to bf16 for the P V
 // product as in the event forward; m, l and acc are fp32.
 // fp32 form: plain VALU, one workgroup per (head, chunk, row); it exists for the parity tests, not for speed.
+//
+// SLOTS (mh_attn_prefix_partial_slots; DecodeSession(prefix_slots=G), the decode pool): G prompts, kpre / vpre [G, H, Pmax, 64],
+// and every row of the batch at a position of its own.  slot_len [G] (0: an empty slot), row_slot [B] (-1, or any value outside
+// [0, G): the row shares nothing) and row_pos [B] are device int32 arrays.  The grid gains a dimension -- blockIdx.y is the slot --
+// and a workgroup serves the MEMBER rows of its slot only: every wave walks row_slot 64 rows at a time, a ballot per step, and
+// wave 0 leaves the members' row ids in LDS in ascending order (behind the merge area; 4 B bytes).  The tiles of 32 query rows are
+// then tiles of that list, each lane's row rotated at its own row_pos, and a partial goes to the workspace index of its ROW,
+// ((b H + h) nch + c), so the consumer's addressing is the uniform form's.  A slot without members, like a chunk past the slot's
+// length, returns at once.  One body serves both forms (`if constexpr`): per query row the arithmetic and its order are the same,
+// and an MFMA output column depends on its own query column alone, so a member row's partial is bit for bit the uniform
+// kernel's for that row at that (pre_len, pos), whatever else shares its tile.
 #include "attn_mfma_common.h"
 
 constexpr int PREFIX_CHUNK = MH_ATTN_PREFIX_CHUNK;
@@ -29,23 +40,47 @@ constexpr int PP_TILES = 4 * 2 * TILE64;             // [wave][K | V] tiles
 constexpr int PP_MERGE_ACC = 4 * 64 * 32 * 4;        // [wave][d][row] fp32 (row fastest: lane-consecutive, no bank conflicts)
 constexpr int PP_MERGE_ML = 4 * 2 * 32 * 4;          // [wave][m | l][row]
 constexpr int PP_LDS = PP_TILES + PP_MERGE_ACC + PP_MERGE_ML;
+constexpr int PP_MAX_ROWS = 4096;                    // (slots form) rows of a batch: the member list, 4 bytes a row behind PP_LDS
 
 // workspace: acc [B, H, nch, 64] followed by (m, l) [B, H, nch, 2]; nch = ceil(Pmax / PREFIX_CHUNK)
 __host__ __device__ inline int64_t prefix_ws_floats(int64_t B, int H, int nch) { return B * H * nch * 66; }
 
+// SLOTS: pre_len_dev is slot_len [G], pos_dev is row_pos [B], row_slot [B] names each row's slot (the host values are not read)
+template <bool SLOTS>
 __global__ __launch_bounds__(256) void attn_prefix_partial_mfma_kernel(
     const bf16* __restrict__ qkv, const float* __restrict__ cos_t, const float* __restrict__ sin_t,
     const bf16* __restrict__ kpre, const bf16* __restrict__ vpre, float* __restrict__ ws, int B, int H, int Pmax, int nch,
-    int pre_len, int pos, float scale, const int32_t* __restrict__ pre_len_dev, const int32_t* __restrict__ pos_dev) {
+    int pre_len, int pos, float scale, const int32_t* __restrict__ pre_len_dev, const int32_t* __restrict__ pos_dev,
+    const int32_t* __restrict__ row_slot) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  if (pre_len_dev != nullptr) pre_len = *pre_len_dev;  // graph replay: both live in device memory
-  if (pos_dev != nullptr) pos = *pos_dev;
+  if constexpr (SLOTS) {
+    pre_len = pre_len_dev[blockIdx.y];
+  } else {
+    if (pre_len_dev != nullptr) pre_len = *pre_len_dev;  // graph replay: both live in device memory
+    if (pos_dev != nullptr) pos = *pos_dev;
+  }
   if (pre_len > Pmax) pre_len = Pmax;
   const int h = blockIdx.x / nch, c = blockIdx.x - h * nch;
   const int k0 = c * PREFIX_CHUNK;
   if (k0 >= pre_len) return;  // (block-uniform) nothing of the prompt in this chunk: no partial, and none is read
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  int nrow = B;  // the query rows this workgroup serves
+  int32_t* members = reinterpret_cast<int32_t*>(smem + PP_LDS);  // (SLOTS) their row ids, ascending
+  if constexpr (SLOTS) {
+    const int g = blockIdx.y;
+    nrow = 0;  // (wave-uniform, and the same in all four waves: each walks the whole of row_slot)
+    for (int b0 = 0; b0 < B; b0 += 64) {
+      const int b = b0 + lane;
+      const bool in = b < B && row_slot[b] == g;
+      const unsigned long long bal = __ballot(in);
+      if (in && wave == 0) members[nrow + __popcll(bal & ((1ull << lane) - 1ull))] = b;
+      nrow += __popcll(bal);
+    }
+    if (nrow == 0) return;  // (block-uniform) no row continues this slot's prompt
+    kpre += (int64_t)g * H * Pmax * HD;
+    vpre += (int64_t)g * H * Pmax * HD;
+  }
   const int kw0 = k0 + 64 * wave;
   const bool live = kw0 < pre_len;  // (wave-uniform) key kw0 is then a real one: every row's maximum is finite
   char* tK = smem + wave * 2 * TILE64;
@@ -98,11 +133,16 @@ __global__ __launch_bounds__(256) void attn_prefix_partial_mfma_kernel(
   float* mg_ml = reinterpret_cast<float*>(smem + PP_TILES + PP_MERGE_ACC);
   const int64_t D = (int64_t)H * HD;
   float* ws_ml = ws + (int64_t)B * H * nch * 64;
-  const int nqt = (B + 31) / 32;
+  const int nqt = (nrow + 31) / 32;
   for (int qt = 0; qt < nqt; ++qt) {
     if (live) {
       int bq = qt * 32 + li;
-      bq = bq < B ? bq : B - 1;
+      bq = bq < nrow ? bq : nrow - 1;
+      if constexpr (SLOTS) {  // (the list was written before the barrier above)
+        bq = members[bq];
+        pos = pos_dev[bq];
+        pos = pos > 0 ? pos : 0;
+      }
       const bf16* qp = qkv + (int64_t)bq * 3 * D + (int64_t)h * HD + 8 * hi;
       bf16x8 raw[4], qf[4];
 #pragma unroll
@@ -166,7 +206,9 @@ __global__ __launch_bounds__(256) void attn_prefix_partial_mfma_kernel(
     __syncthreads();
     {  // the four waves' states -> one partial per row: thread = (row q, eight consecutive d)
       const int q = tid & 31, dg = tid >> 5;
-      const int bq = qt * 32 + q;
+      int bq = qt * 32 + q;
+      const bool real = bq < nrow;  // (not a padding row of the last tile)
+      if constexpr (SLOTS) bq = members[real ? bq : 0];
       float mw[4], f[4], gm = -INFINITY, lsum = 0.f;
 #pragma unroll
       for (int w = 0; w < 4; ++w) {
@@ -178,7 +220,7 @@ __global__ __launch_bounds__(256) void attn_prefix_partial_mfma_kernel(
         f[w] = (mw[w] == -INFINITY) ? 0.f : fast_exp2((mw[w] - gm) * LOG2E);
         lsum += mg_ml[(w * 2 + 1) * 32 + q] * f[w];
       }
-      if (bq < B) {
+      if (real) {
         float out[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -205,13 +247,25 @@ __global__ __launch_bounds__(256) void attn_prefix_partial_mfma_kernel(
 }
 
 // fp32 (parity) form: grid (H * nch, B), thread = key of the chunk.
-template <typename T>
+// SLOTS: the arguments as in the MFMA form; the row looks its own slot up (G slots), and a row without one returns at once.
+template <typename T, bool SLOTS = false>
 __global__ __launch_bounds__(256) void attn_prefix_partial_valu_kernel(
     const T* __restrict__ qkv, const float* __restrict__ cos_t, const float* __restrict__ sin_t, const T* __restrict__ kpre,
     const T* __restrict__ vpre, float* __restrict__ ws, int B, int H, int Pmax, int nch, int pre_len, int pos, float scale,
-    const int32_t* __restrict__ pre_len_dev, const int32_t* __restrict__ pos_dev) {
-  if (pre_len_dev != nullptr) pre_len = *pre_len_dev;
-  if (pos_dev != nullptr) pos = *pos_dev;
+    const int32_t* __restrict__ pre_len_dev, const int32_t* __restrict__ pos_dev, const int32_t* __restrict__ row_slot = nullptr,
+    int G = 0) {
+  if constexpr (SLOTS) {
+    const int g = row_slot[blockIdx.y];
+    if (g < 0 || g >= G) return;
+    pre_len = pre_len_dev[g];
+    pos = pos_dev[blockIdx.y];
+    pos = pos > 0 ? pos : 0;
+    kpre += (int64_t)g * H * Pmax * 64;
+    vpre += (int64_t)g * H * Pmax * 64;
+  } else {
+    if (pre_len_dev != nullptr) pre_len = *pre_len_dev;
+    if (pos_dev != nullptr) pos = *pos_dev;
+  }
   if (pre_len > Pmax) pre_len = Pmax;
   const int h = blockIdx.x / nch, c = blockIdx.x - h * nch, b = blockIdx.y;
   const int k0 = c * PREFIX_CHUNK;
@@ -290,7 +344,7 @@ extern "C" int mh_attn_prefix_partial(const void* qkv, const float* cos_t, const
       return MH_ERR_LAUNCH;
     }
     if (!__atomic_load_n(&attr_set_of[dev], __ATOMIC_ACQUIRE)) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_prefix_partial_mfma_kernel),
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_prefix_partial_mfma_kernel<false>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS);
       if (e != hipSuccess) {
         mh_set_error("attn_prefix_partial: cannot raise dynamic LDS to %d bytes: %s", PP_LDS, hipGetErrorString(e));
@@ -298,13 +352,67 @@ extern "C" int mh_attn_prefix_partial(const void* qkv, const float* cos_t, const
       }
       __atomic_store_n(&attr_set_of[dev], true, __ATOMIC_RELEASE);
     }
-    attn_prefix_partial_mfma_kernel<<<H * nch, 256, PP_LDS, st>>>((const bf16*)qkv, cos_t, sin_t, (const bf16*)kpre,
-                                                                  (const bf16*)vpre, ws, (int)B, H, (int)Pmax, nch, (int)pre_len,
-                                                                  (int)pos, scale, pre_len_dev, pos_dev);
+    attn_prefix_partial_mfma_kernel<false><<<H * nch, 256, PP_LDS, st>>>((const bf16*)qkv, cos_t, sin_t, (const bf16*)kpre,
+                                                                         (const bf16*)vpre, ws, (int)B, H, (int)Pmax, nch,
+                                                                         (int)pre_len, (int)pos, scale, pre_len_dev, pos_dev, nullptr);
   } else {
     attn_prefix_partial_valu_kernel<float><<<dim3(H * nch, (unsigned)B), 256, 0, st>>>(
         (const float*)qkv, cos_t, sin_t, (const float*)kpre, (const float*)vpre, ws, (int)B, H, (int)Pmax, nch, (int)pre_len,
         (int)pos, scale, pre_len_dev, pos_dev);
+  }
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// The slots form (the header of this file): G prompts, every row at its own position and in at most one slot.
+extern "C" int mh_attn_prefix_partial_slots(const void* qkv, const float* cos_t, const float* sin_t, const void* kpre,
+                                            const void* vpre, const int32_t* slot_len, const int32_t* row_slot,
+                                            const int32_t* row_pos, float* ws, int64_t ws_floats, int64_t B, int H, int hd,
+                                            int64_t G, int64_t Pmax, float scale, int dtype, void* stream) {
+  MH_REQUIRE(hd == 64, "attn_prefix_partial_slots: head_dim %d unsupported (64)", hd);
+  MH_REQUIRE(dtype == MH_BF16 || dtype == MH_F32, "attn_prefix_partial_slots: bad dtype %d", dtype);
+  MH_REQUIRE(qkv != nullptr, "attn_prefix_partial_slots: qkv is NULL");
+  MH_REQUIRE(cos_t != nullptr && sin_t != nullptr, "attn_prefix_partial_slots: a rope table is NULL (qkv arrives unrotated)");
+  MH_REQUIRE(kpre != nullptr && vpre != nullptr, "attn_prefix_partial_slots: kpre or vpre is NULL");
+  MH_REQUIRE(slot_len != nullptr, "attn_prefix_partial_slots: slot_len is NULL (one device int32 length per slot)");
+  MH_REQUIRE(row_slot != nullptr, "attn_prefix_partial_slots: row_slot is NULL (one device int32 slot id per row, -1: none)");
+  MH_REQUIRE(row_pos != nullptr, "attn_prefix_partial_slots: row_pos is NULL (one device int32 position per row)");
+  MH_REQUIRE(ws != nullptr, "attn_prefix_partial_slots: ws is NULL");
+  MH_REQUIRE(G >= 1 && G <= 65535, "attn_prefix_partial_slots: %ld slots (1 to 65535)", (long)G);
+  MH_REQUIRE(B > 0 && B <= PP_MAX_ROWS && H > 0 && Pmax > 0 && Pmax < (1 << 24),
+             "attn_prefix_partial_slots: bad args B=%ld (at most %d: a slot's member list lives in LDS) H=%d Pmax=%ld", (long)B,
+             PP_MAX_ROWS, H, (long)Pmax);
+  const int nch = (int)((Pmax + PREFIX_CHUNK - 1) / PREFIX_CHUNK);
+  MH_REQUIRE(ws_floats >= prefix_ws_floats(B, H, nch), "attn_prefix_partial_slots: workspace of %ld floats, %ld needed",
+             (long)ws_floats, (long)prefix_ws_floats(B, H, nch));
+  MH_REQUIRE((int64_t)H * nch < (1 << 30), "attn_prefix_partial_slots: grid too large");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == MH_BF16) {
+    constexpr int MAX_DEV = 64;
+    constexpr int LDS_MAX = PP_LDS + 4 * PP_MAX_ROWS;
+    static bool attr_set_of[MAX_DEV];
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) {
+      mh_set_error("attn_prefix_partial_slots: no current device (or ordinal %d beyond %d)", dev, MAX_DEV - 1);
+      return MH_ERR_LAUNCH;
+    }
+    if (!__atomic_load_n(&attr_set_of[dev], __ATOMIC_ACQUIRE)) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_prefix_partial_mfma_kernel<true>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+      if (e != hipSuccess) {
+        mh_set_error("attn_prefix_partial_slots: cannot raise dynamic LDS to %d bytes: %s", LDS_MAX, hipGetErrorString(e));
+        return MH_ERR_LAUNCH;
+      }
+      __atomic_store_n(&attr_set_of[dev], true, __ATOMIC_RELEASE);
+    }
+    const int lds = PP_LDS + 4 * (int)((B + 63) / 64 * 64);
+    attn_prefix_partial_mfma_kernel<true><<<dim3(H * nch, (unsigned)G), 256, lds, st>>>(
+        (const bf16*)qkv, cos_t, sin_t, (const bf16*)kpre, (const bf16*)vpre, ws, (int)B, H, (int)Pmax, nch, 0, 0, scale, slot_len,
+        row_pos, row_slot);
+  } else {
+    attn_prefix_partial_valu_kernel<float, true><<<dim3(H * nch, (unsigned)B), 256, 0, st>>>(
+        (const float*)qkv, cos_t, sin_t, (const float*)kpre, (const float*)vpre, ws, (int)B, H, (int)Pmax, nch, 0, 0, scale,
+        slot_len, row_pos, row_slot, (int)G);
   }
   MH_LAUNCH_CHECK();
   return MH_OK;

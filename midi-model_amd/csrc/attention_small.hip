@@ -787,8 +787,11 @@ __device__ inline float group_sum(float v) {
 // new row goes to suffix row pos - pre_len, the key loop covers suffix rows [0, pos - pre_len], and before normalising the
 // block adds the ceil(pre_len / chunk) partials (acc[HD], m, l) that mh_attn_prefix_partial left for its (b, h), in chunk order.
 // The trailing arguments are read by SHARED instantiations only.
-// ROWS (generate_ragged; not with SHARED): sequence b sits at a position of its own, pos_dev[b] (device int32 [B]).  The grid is
+// ROWS (generate_ragged): sequence b sits at a position of its own, pos_dev[b] (device int32 [B]).  The grid is
 // (H, B) -- blockIdx.y is the sequence -- so the position is one scalar load per workgroup, issued with the argument fetch.
+// ROWS with SHARED (APPEND only; DecodeSession(prefix_slots=G), mh_attn_prefix_partial_slots): the prompt a row shares is the one
+// in slot row_slot[b] of n_slots, pre_len_dev is slot_len [n_slots], and pre_b = min(slot_len[row_slot[b]], pre_max), or 0 for a
+// row whose row_slot lies outside [0, n_slots).  Such a row merges no partial: it does the arithmetic of the plain ROWS form.
 template <typename T, int HD, bool APPEND, bool SHARED = false, bool ROWS = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ qkv, T* kc, T* vc, T* __restrict__ o, int H,
                                                           int64_t Lmax, int64_t len, float scale,
@@ -796,9 +799,9 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
                                                           const float* __restrict__ cos_t, const float* __restrict__ sin_t,
                                                           const float* __restrict__ part = nullptr, int nch = 0, int chunk = 1,
                                                           int pre_len = 0, const int32_t* __restrict__ pre_len_dev = nullptr,
-                                                          int64_t n_bh = 0) {
+                                                          int64_t n_bh = 0, const int32_t* __restrict__ row_slot = nullptr,
+                                                          int n_slots = 0, int pre_max = 0) {
   static_assert(!SHARED || APPEND, "the shared-prefix form appends");
-  static_assert(!ROWS || !SHARED, "per-row positions: the plain cache only");
   // every kernel argument fetched at entry in one batch (hipcc sinks each s_load into the block that first uses it otherwise:
   // a scalar-cache miss + wait per block on a kernel whose whole run is a few microseconds)
   asm volatile("" ::"s"(qkv), "s"(kc), "s"(vc), "s"(o), "s"(H), "s"(Lmax), "s"(len), "s"(scale));
@@ -811,7 +814,17 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
   }
   int64_t rpos = len - 1;  // the position RoPE runs at
   if constexpr (SHARED) {
-    if (pre_len_dev != nullptr) pre_len = *pre_len_dev;
+    if constexpr (ROWS) {
+      const int slot = row_slot[blockIdx.y];
+      pre_len = 0;
+      if (slot >= 0 && slot < n_slots) {
+        pre_len = pre_len_dev[slot];
+        pre_len = pre_len < pre_max ? pre_len : pre_max;
+        pre_len = pre_len > 0 ? pre_len : 0;
+      }
+    } else {
+      if (pre_len_dev != nullptr) pre_len = *pre_len_dev;
+    }
     len -= pre_len;  // suffix rows [0, pos - pre_len]
     if (len < 1) len = 1;
   }
@@ -1107,6 +1120,41 @@ extern "C" int mh_attn_decode_append_shared(const void* qkv, const float* cos_t,
     attn_decode_kernel<float, 64, true, true><<<grid, 256, 0, st>>>((const float*)qkv, (float*)ksuf, (float*)vsuf, (float*)o, H,
                                                                     Lsuf, pos + 1, scale, pos_dev, cos_t, sin_t, ws, nch,
                                                                     MH_ATTN_PREFIX_CHUNK, (int)pre_len, pre_len_dev, B * H);
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// The suffix half over prefix SLOTS (attention_shared.hip: mh_attn_prefix_partial_slots left the partials): every row at its own
+// position and behind the prompt of its own slot, or of none.
+extern "C" int mh_attn_decode_append_rows_shared(const void* qkv, const float* cos_t, const float* sin_t, void* ksuf, void* vsuf,
+                                                 const float* ws, int64_t ws_floats, void* o, int64_t B, int H, int hd,
+                                                 int64_t Lsuf, int64_t G, int64_t Pmax, float scale, const int32_t* slot_len,
+                                                 const int32_t* row_slot, const int32_t* row_pos, int dtype, void* stream) {
+  MH_REQUIRE(hd == 64, "attn_decode_append_rows_shared: head_dim %d unsupported (64)", hd);
+  MH_REQUIRE(dtype == MH_BF16 || dtype == MH_F32, "attn_decode_append_rows_shared: bad dtype %d", dtype);
+  MH_REQUIRE(qkv != nullptr && o != nullptr, "attn_decode_append_rows_shared: qkv or o is NULL");
+  MH_REQUIRE(cos_t != nullptr && sin_t != nullptr, "attn_decode_append_rows_shared: a rope table is NULL (qkv arrives unrotated)");
+  MH_REQUIRE(ksuf != nullptr && vsuf != nullptr, "attn_decode_append_rows_shared: ksuf or vsuf is NULL");
+  MH_REQUIRE(ws != nullptr, "attn_decode_append_rows_shared: ws is NULL");
+  MH_REQUIRE(slot_len != nullptr, "attn_decode_append_rows_shared: slot_len is NULL (one device int32 length per slot)");
+  MH_REQUIRE(row_slot != nullptr, "attn_decode_append_rows_shared: row_slot is NULL (one device int32 slot id per row, -1: none)");
+  MH_REQUIRE(row_pos != nullptr, "attn_decode_append_rows_shared: row_pos is NULL (one device int32 position per row)");
+  MH_REQUIRE(G >= 1 && G <= 65535, "attn_decode_append_rows_shared: %ld slots (1 to 65535)", (long)G);
+  MH_REQUIRE(B > 0 && B <= 65535 && H > 0 && Lsuf > 0 && Lsuf < (1 << 24) && Pmax > 0 && Pmax < (1 << 24),
+             "attn_decode_append_rows_shared: bad args B=%ld H=%d Lsuf=%ld Pmax=%ld", (long)B, H, (long)Lsuf, (long)Pmax);
+  const int nch = (int)((Pmax + MH_ATTN_PREFIX_CHUNK - 1) / MH_ATTN_PREFIX_CHUNK);
+  MH_REQUIRE(ws_floats >= B * H * nch * 66, "attn_decode_append_rows_shared: workspace of %ld floats, %ld needed", (long)ws_floats,
+             (long)(B * H * nch * 66));
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)H, (unsigned)B);
+  if (dtype == MH_BF16)
+    attn_decode_kernel<bf16, 64, true, true, true><<<grid, 256, 0, st>>>(
+        (const bf16*)qkv, (bf16*)ksuf, (bf16*)vsuf, (bf16*)o, H, Lsuf, 0, scale, row_pos, cos_t, sin_t, ws, nch,
+        MH_ATTN_PREFIX_CHUNK, 0, slot_len, B * H, row_slot, (int)G, (int)Pmax);
+  else
+    attn_decode_kernel<float, 64, true, true, true><<<grid, 256, 0, st>>>(
+        (const float*)qkv, (float*)ksuf, (float*)vsuf, (float*)o, H, Lsuf, 0, scale, row_pos, cos_t, sin_t, ws, nch,
+        MH_ATTN_PREFIX_CHUNK, 0, slot_len, B * H, row_slot, (int)G, (int)Pmax);
   MH_LAUNCH_CHECK();
   return MH_OK;
 }

@@ -83,6 +83,18 @@ Stale K/V at cache rows >= lengths[p] of a destination is never read, by the arg
 PARKED: the net steps that follow keep writing its cache row max_len and its ``hidden``, never rows [0, max_len).  ``hold(rows)``
 therefore copies ``hidden[rows]`` into ``held_hidden`` right behind the net step over the row's last event, and a later
 ``fork(from_held=...)`` takes ``hidden`` from there: a held row can be continued any number of steps later.
+
+``prefix_slots`` = G > 0 with ``prefix_capacity`` = Pmax (row_params sessions; decode_pool(prefix_slots=...)): rows may
+SHARE a prompt's K/V.  ``kvs`` holds G prefix slots of Pmax rows per layer ([G, H, Pmax, 64]), ``slot_len`` (int32 [G]; 0: empty)
+their lengths and ``row_slot`` (int32 [B]; -1: none) the slot each row continues; a sharing row's own cache ``kv1`` holds only what
+lies BEHIND its slot's prompt -- cache row j is absolute position slot_len[row_slot[b]] + j -- while ``pos`` and ``pos_limit`` stay
+absolute.  The net step's attention is the two launches of ops_share.py for EVERY row (a row without a slot merges no partial and
+does the per-row kernel's arithmetic).  The graphs read the three arrays at replay time and their geometry depends on (B, capacity,
+G, Pmax) only: nothing is recaptured.  ``admit(slots=...)`` stores the admitted prompts' K/V into slots instead of rows;
+``fork(join=...)`` lets a destination join its source's slot and copies only the source's own cache rows [0, pos - pre) -- nothing
+when that is empty; ``release`` frees a slot (slot_len = 0, in stream order) when its last row leaves, a held row keeping its slot.
+The host keeps the slot of every row, every slot's length and its reference count (``slot_refs``): it decides which slot is free.
+``prefix_slots=0`` is the session as it was: no new buffer, no new key, the same launches.
 """
 from __future__ import annotations
 
@@ -115,7 +127,8 @@ def graphs_enabled(device: torch.device) -> bool:
 
 class DecodeSession:
     def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int, shared_capacity: int = 0,
-                 ragged: bool = False, row_params: bool = False, seeded: bool = False):
+                 ragged: bool = False, row_params: bool = False, seeded: bool = False, prefix_slots: int = 0,
+                 prefix_capacity: int = 0):
         tok = model.tokenizer
         self.model, self.B, self.cap, self.temp = model, B, capacity, float(temp)
         self.top_p, self.top_k = float(top_p), int(top_k)
@@ -123,7 +136,9 @@ class DecodeSession:
         self.ragged = bool(ragged)
         self.row_params = bool(row_params)
         self.seeded = bool(seeded)
-        self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params, seeded)
+        self.prefix_slots, self.prefix_capacity = int(prefix_slots), int(prefix_capacity)
+        self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params, seeded,
+                                 prefix_slots, prefix_capacity)
         dev, dt = model.device, model.dtype
         self.T, self.V, self.Vp = tok.max_token_seq, tok.vocab_size, model.vocab_padded
         spec, tspec = model._specs["net"], model._specs["net_token"]
@@ -135,6 +150,15 @@ class DecodeSession:
             self.kvp = KVState(spec, 1, self.shared_capacity, model._flat)  # the prompt, once
             self.pre_len = torch.zeros(1, dtype=torch.int32, device=dev)      # its length (device side, beside pos)
             self.ws = torch.empty(shared.workspace_floats(B, spec.H, self.shared_capacity), dtype=torch.float32, device=dev)
+        self.kvs = self.slot_len = self.row_slot = None
+        if self.prefix_slots > 0:
+            from .ops_share import workspace_floats
+            G, Pmax = self.prefix_slots, self.prefix_capacity
+            self.kvs = KVState(spec, G, Pmax, model._flat)                        # the G shared prompts, once each
+            self.slot_len = torch.zeros(G, dtype=torch.int32, device=dev)        # their lengths (0: the slot is empty)
+            self.row_slot = torch.full((B,), -1, dtype=torch.int32, device=dev)  # the slot each row continues (-1: none)
+            self.ws = torch.empty(workspace_floats(B, spec.H, Pmax), dtype=torch.float32, device=dev)
+            self._reset_slots_host()
         # rope tables private to the session: a captured graph keeps their addresses
         self.rope1 = RopeTable(spec.hd, spec.theta, dev, capacity + self.shared_capacity)
         self.rope2 = RopeTable(tspec.hd, tspec.theta, dev, self.T)
@@ -206,7 +230,14 @@ class DecodeSession:
             self._capture()
 
     @staticmethod
-    def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False, row_params=False, seeded=False):
+    def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False, row_params=False, seeded=False,
+                 prefix_slots=0, prefix_capacity=0):
+        if prefix_slots or prefix_capacity:
+            if not (ragged and row_params) or int(prefix_slots) != prefix_slots or int(prefix_capacity) != prefix_capacity \
+                    or prefix_slots < 1 or prefix_capacity < 1:
+                raise ValueError(f"DecodeSession: prefix_slots={prefix_slots!r}, prefix_capacity={prefix_capacity!r} -- prefix slots "
+                                 "are a form of the per-row session (ragged=True, row_params=True) and need at least one slot of "
+                                 "at least one row")
         if ragged and shared_capacity:
             raise ValueError("DecodeSession: ragged rows have prompts of their own -- not together with a shared prompt")
         if seeded and not (ragged and row_params):
@@ -217,6 +248,8 @@ class DecodeSession:
                                  "without ragged=True")
             # no temperature, top-p or top-k: they are buffer contents of this form, not facts of its graphs (nor is a seed)
             form = ("ragged", "row_params", "seeded") if seeded else ("ragged", "row_params")
+            if prefix_slots:  # (no existing key changes: a session without slots keeps the key it had)
+                form += (("slots", int(prefix_slots), int(prefix_capacity)),)
             return (model._flat.data_ptr(), model._flat.dtype, B, capacity, form)
         key = (model._flat.data_ptr(), model._flat.dtype, B, capacity, float(temp), float(top_p), int(top_k))
         if ragged:
@@ -243,8 +276,12 @@ class DecodeSession:
         e = torch.empty((self.B, spec.D), dtype=m.dtype, device=m.device)
         ops.embed_sum_fwd(self.seq, m._W["net"].embed, e)  # the event sampled last
         if self.ragged:  # every row at its own position; a row at pos_limit stays there
+            sh = None
+            if self.kvs is not None:  # ... and behind the prompt of its slot, if it names one
+                from .ops_share import SlotPrefix
+                sh = SlotPrefix(self.kvs, self.slot_len, self.row_slot, self.ws)
             engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, folded=self.fold1, out=self.hidden, row_pos=self.pos,
-                                wide=self.wide)
+                                wide=self.wide, shared=sh)
             self.pos.add_(1)
             torch.minimum(self.pos, self.pos_limit, out=self.pos)
             return
@@ -395,6 +432,20 @@ class DecodeSession:
         if self.kvp is not None:
             self.kvp.len = 0
             self.pre_len.zero_()
+        if self.kvs is not None:
+            self.slot_len.zero_()
+            self.row_slot.fill_(-1)
+            self._reset_slots_host()
+
+    def _reset_slots_host(self) -> None:
+        """(prefix slots) the host's books: no row names a slot, every slot is empty and free"""
+        self.row_slot_host = [-1] * self.B                 # row -> its slot
+        self.slot_len_host = [0] * self.prefix_slots       # slot -> the length of its prompt
+        self.slot_refs = [0] * self.prefix_slots           # slot -> rows that name it (running and held)
+
+    def free_slots(self) -> List[int]:
+        """(prefix slots) the slots no row names, ascending"""
+        return [g for g, n in enumerate(self.slot_refs) if n == 0] if self.kvs is not None else []
 
     def prefill(self, tokens: torch.Tensor) -> None:
         """tokens [B, S, T]: causal forward over the prompt from an empty cache; leaves hidden = last position.
@@ -504,7 +555,8 @@ class DecodeSession:
         self.hidden.copy_(y.index_select(0, plan.seq_start[1:].long() - 1))
         self.pos.copy_(plan.seq_start[1:] - plan.seq_start[:-1])
 
-    def admit(self, rows, tokens: torch.Tensor, lengths, limits, temp, top_p, top_k, first_masks, bans, seeds=None) -> None:
+    def admit(self, rows, tokens: torch.Tensor, lengths, limits, temp, top_p, top_k, first_masks, bans, seeds=None,
+              slots=None) -> None:
         """(row_params) n new requests into rows ``rows`` of the running batch, between two events (the header has the stream-order
         argument).  tokens [M, T]: the n prompts laid end to end, prompt s of lengths[s] events; limits[s]: the position row
         rows[s] is parked at (its max_len); temp / top_p / top_k: n values; first_masks / bans: uint8 [n, V] (host).  ONE packed
@@ -514,7 +566,13 @@ class DecodeSession:
         arrays and both masks of those rows overwritten.  The per-row values travel in ONE pinned host block and are scattered by
         eight index_copy_ calls (and one index_select for the last positions): no kernel of their own.  A seeded session takes
         ``seeds`` as well, n ints in [0, 2^64): one more int64 section of the block and a ninth index_copy_ into ``seed_rows``; an
-        unseeded session refuses them.  Everything is checked on the host first; ``ValueError`` before any launch."""
+        unseeded session refuses them.
+        ``slots`` (a prefix_slots session; n distinct FREE slots, one per sequence -- an admission stores all of its prompts in
+        slots or none, so that either cache takes the one packed store per layer): prompt s's K/V goes into slot slots[s]
+        (mh_kv_store_seqs_rows over the slot cache, the slot ids as the row map) and NOT into cache row rows[s], whose own cache
+        starts empty behind it; ``row_slot[rows]`` = slots and ``slot_len[slots]`` = lengths travel in the same block (two more
+        index_copy_ calls).  Without ``slots`` such a session sets ``row_slot[rows]`` = -1.
+        Everything is checked on the host first; ``ValueError`` before any launch."""
         if not (self.ragged and self.row_params):
             raise ValueError("DecodeSession.admit: rows are admitted into a ragged=True, row_params=True session only")
         from .ops_pool import check_rows
@@ -542,6 +600,18 @@ class DecodeSession:
             seed_vals = self._seed_values(seeds, n, "admit")
         elif seeds is not None:
             raise ValueError("admit: seeds are taken by a seeded=True session only")
+        slot_ids = None
+        if slots is not None:
+            if self.kvs is None:
+                raise ValueError("admit: slots are taken by a session with prefix slots only (prefix_slots=G, prefix_capacity=Pmax)")
+            from .ops_share import check_slots
+            slot_ids = check_slots(slots, n, self.prefix_slots)
+            if any(self.slot_refs[g] for g in slot_ids):
+                raise ValueError(f"admit: slots {[g for g in slot_ids if self.slot_refs[g]]} are in use")
+            if max(lengths) > self.prefix_capacity:
+                raise ValueError(f"admit: a prompt of {max(lengths)} events into a prefix slot of {self.prefix_capacity}")
+        if self.kvs is not None and any(self.row_slot_host[r] >= 0 for r in ids):
+            raise ValueError(f"admit: rows {[r for r in ids if self.row_slot_host[r] >= 0]} still name a prefix slot: release them first")
         # ---- the one host block: [idx i64 | last i64 | rows i32 | lengths i32 | limits i32 | top_k i32 | temp f32 | top_p f32 |
         #      first u8 | ban u8 (| seeds i64)], every section on a multiple of 16 bytes
         sections = [(np.int64, ids), (np.int64, np.cumsum(lengths) - 1), (np.int32, ids), (np.int32, lengths), (np.int32, limits),
@@ -549,15 +619,23 @@ class DecodeSession:
                     (np.uint8, first_masks.numpy().reshape(-1)), (np.uint8, bans.numpy().reshape(-1))]
         if self.seeded:
             sections.append((np.int64, seed_vals))
+        if slot_ids is not None:  # (| slots i64 | slots i32), behind everything a session without slots stages
+            sections += [(np.int64, slot_ids), (np.int32, slot_ids)]
         dev = m.device
-        idx, last, rows_dev, len_dev, lim_dev, k_dev, t_dev, p_dev, first_dev, ban_dev, *seed_dev = \
+        idx, last, rows_dev, len_dev, lim_dev, k_dev, t_dev, p_dev, first_dev, ban_dev, *more_dev = \
             self._stage_block(sections, "_admit_stage")
+        seed_dev = more_dev[:1] if self.seeded else []
         # ---- one packed forward over the admitted prompts alone, K/V into the chosen cache rows
         plan = ops.attn_seq_plan(lengths, spec.H).upload(dev)
         e = torch.empty((M, spec.D), dtype=m.dtype, device=dev)
         ops.embed_sum_fwd(tokens.to(dev).contiguous(), m._W["net"].embed, e)
-        y = engine.stack_prefill_seqs(spec, m._W["net"], e, plan, self.rope1, self.kv1, folded=self.fold1, rows=ids,
-                                      rows_dev=rows_dev)
+        if slot_ids is not None:  # the prompts' K/V into their slots; the rows' own caches start empty behind them
+            slot_idx, slots_dev = more_dev[-2:]
+            y = engine.stack_prefill_seqs(spec, m._W["net"], e, plan, self.rope1, self.kvs, folded=self.fold1, rows=slot_ids,
+                                          rows_dev=slots_dev)
+        else:
+            y = engine.stack_prefill_seqs(spec, m._W["net"], e, plan, self.rope1, self.kv1, folded=self.fold1, rows=ids,
+                                          rows_dev=rows_dev)
         # ---- the rows' state
         self.hidden.index_copy_(0, idx, y.index_select(0, last))
         self.pos.index_copy_(0, idx, len_dev)
@@ -569,6 +647,13 @@ class DecodeSession:
         self.ban.index_copy_(0, idx, ban_dev.view(n, V))
         if self.seeded:
             self.seed_rows.index_copy_(0, idx, seed_dev[0])
+        if slot_ids is not None:
+            self.row_slot.index_copy_(0, idx, slots_dev)
+            self.slot_len.index_copy_(0, slot_idx, len_dev)
+            for r, g, L in zip(ids, slot_ids, lengths):
+                self.row_slot_host[r], self.slot_len_host[g], self.slot_refs[g] = g, L, 1
+        elif self.kvs is not None:
+            self.row_slot.index_fill_(0, idx, -1)
 
     _STAGE_TYPES = {np.int64: torch.int64, np.int32: torch.int32, np.float32: torch.float32, np.uint8: torch.uint8}
 
@@ -591,7 +676,8 @@ class DecodeSession:
             block = getattr(self, slot).to(self.model.device, non_blocking=True)
         return [block[o:o + sz].view(self._STAGE_TYPES[ty]) for (ty, _), (o, sz) in zip(sections, offs)]
 
-    def fork(self, src_rows, dst_rows, lengths, limits, temp, top_p, top_k, first_masks, bans, seeds=None, from_held=None) -> None:
+    def fork(self, src_rows, dst_rows, lengths, limits, temp, top_p, top_k, first_masks, bans, seeds=None, from_held=None,
+             join=None) -> None:
         """(row_params) n rows of the running batch become continuations of other rows, between two events, WITHOUT a forward (the
         header has the stream-order argument).  For pair p: cache rows [0, lengths[p]) of every layer of sequence src_rows[p] are
         copied to sequence dst_rows[p] -- ONE mh_kv_fork_rows launch over the whole of ``kv1`` -- and row dst_rows[p] takes
@@ -600,7 +686,12 @@ class DecodeSession:
         them).  lengths[p] is the number of events whose K/V the source row holds: the caller's to know -- the session keeps no
         host copy of ``pos``.  Several pairs may name one source; the dst rows are distinct and no row stands on both sides.
         The per-row values travel in ONE pinned host block and are scattered by index_copy_ calls, as in ``admit``.  No forward,
-        no capture, no recapture: every buffer sits at the address the graphs hold.  ``ValueError`` before any launch."""
+        no capture, no recapture: every buffer sits at the address the graphs hold.
+        ``join`` (a prefix_slots session; a bool per pair): dst_rows[p] JOINS the slot of src_rows[p] -- ``row_slot[dst]`` = the
+        source's slot, one more reference to it -- and only the source's own cache rows [0, lengths[p] - pre), pre the slot's
+        length, are copied: the launch covers the pairs with a row to copy, and when there is none it is not made.  A source that
+        names a slot can only be forked with ``join``; a source that names none only without.
+        ``ValueError`` before any launch."""
         if not (self.ragged and self.row_params):
             raise ValueError("DecodeSession.fork: rows are forked in a ragged=True, row_params=True session only")
         from .ops_fork import check_pairs
@@ -630,6 +721,26 @@ class DecodeSession:
             raise ValueError(f"fork: from_held holds {len(held)} values for {n} pairs")
         if any(held) and self.held_hidden is None:
             raise ValueError("fork: from_held names a row, and hold() has kept none")
+        copies = None  # (join) the pairs with rows of their own to copy, as (src, dst, rows); None: every pair, lengths[p] rows
+        if join is not None or self.kvs is not None:
+            joins = [bool(x) for x in join] if join is not None else [False] * n
+            if len(joins) != n:
+                raise ValueError(f"fork: join holds {len(joins)} values for {n} pairs")
+            if any(joins) and self.kvs is None:
+                raise ValueError("fork: join is taken by a session with prefix slots only")
+            if self.kvs is not None:
+                src_slot = [self.row_slot_host[s] for s in src]
+                if any((g >= 0) != j for g, j in zip(src_slot, joins)):
+                    raise ValueError(f"fork: sources {src} name the slots {src_slot} and join is {joins}: a child of a row that shares "
+                                     "a prompt joins its slot, and no other child does")
+                if any(self.row_slot_host[d] >= 0 for d in dst):
+                    raise ValueError(f"fork: destination rows {[d for d in dst if self.row_slot_host[d] >= 0]} still name a prefix "
+                                     "slot: release them first")
+                pre = [self.slot_len_host[g] if g >= 0 else 0 for g in src_slot]
+                if any(L < p for L, p in zip(lengths, pre)):
+                    raise ValueError(f"fork: rows of {lengths} events behind prompts of {pre}")
+                if any(joins):
+                    copies = [(s, d, L - p) for s, d, L, p in zip(src, dst, lengths, pre) if L - p > 0]
         # ---- the one host block: [dst i64 | src i64 | src, dst, lengths i32 [3, n] | limits i32 | top_k i32 | temp f32 | top_p f32 |
         #      first u8 | ban u8 | held u8 (| seeds i64)]
         sections = [(np.int64, dst), (np.int64, src), (np.int32, src + dst + lengths), (np.int32, limits), (np.int32, vals[2]),
@@ -637,11 +748,20 @@ class DecodeSession:
                     (np.uint8, bans.numpy().reshape(-1)), (np.uint8, held)]
         if self.seeded:
             sections.append((np.int64, seed_vals))
-        idx, from_idx, pairs, lim_dev, k_dev, t_dev, p_dev, first_dev, ban_dev, held_dev, *seed_dev = \
+        if self.kvs is not None:  # (| slots i32 (| src, dst, rows i32 [3, m] of the pairs to copy)), behind the rest
+            sections.append((np.int32, src_slot))
+            if copies:
+                sections.append((np.int32, [c[k] for k in range(3) for c in copies]))
+        idx, from_idx, pairs, lim_dev, k_dev, t_dev, p_dev, first_dev, ban_dev, held_dev, *more_dev = \
             self._stage_block(sections, "_fork_stage")
+        seed_dev = more_dev[:1] if self.seeded else []
         pairs = pairs.view(3, n)
         # ---- the K/V of every layer, one launch
-        ops.kv_fork_rows(self.kv1.k, self.kv1.v, src, dst, lengths, dev=pairs)
+        if copies is None:
+            ops.kv_fork_rows(self.kv1.k, self.kv1.v, src, dst, lengths, dev=pairs)
+        elif copies:
+            ops.kv_fork_rows(self.kv1.k, self.kv1.v, *([c[k] for c in copies] for k in range(3)),
+                             dev=more_dev[-1].view(3, len(copies)))
         # ---- the rows' state
         h = self.hidden.index_select(0, from_idx)
         if any(held):
@@ -656,6 +776,12 @@ class DecodeSession:
         self.ban.index_copy_(0, idx, ban_dev.view(n, V))
         if self.seeded:
             self.seed_rows.index_copy_(0, idx, seed_dev[0])
+        if self.kvs is not None:
+            self.row_slot.index_copy_(0, idx, more_dev[1 if self.seeded else 0])
+            for d, g in zip(dst, src_slot):
+                self.row_slot_host[d] = g
+                if g >= 0:
+                    self.slot_refs[g] += 1
 
     def hold(self, rows) -> None:
         """(row_params) keep ``hidden[rows]`` -- the net output over those rows' LAST event -- in ``held_hidden`` [B, D] (allocated
@@ -676,7 +802,9 @@ class DecodeSession:
     def release(self, rows) -> None:
         """(row_params) rows whose requests have finished: pos = pos_limit = 0 there.  A free row is still embedded, attended and
         sampled with the rest of the batch, but it now attends to ONE key (the row it overwrites at position 0) instead of
-        dragging a finished request's whole cache through the attention kernel; what it samples is the caller's to drop."""
+        dragging a finished request's whole cache through the attention kernel; what it samples is the caller's to drop.
+        A prefix_slots session: ``row_slot`` = -1 there as well, and a slot whose last row leaves is emptied (``slot_len`` = 0, on
+        the same stream) and free again."""
         if not (self.ragged and self.row_params):
             raise ValueError("DecodeSession.release: rows are released on a ragged=True, row_params=True session only")
         from .ops_pool import check_rows
@@ -686,6 +814,18 @@ class DecodeSession:
         idx = torch.tensor(ids, dtype=torch.int64).to(self.model.device)
         self.pos.index_fill_(0, idx, 0)
         self.pos_limit.index_fill_(0, idx, 0)
+        if self.kvs is not None:
+            self.row_slot.index_fill_(0, idx, -1)
+            emptied = []
+            for r in ids:
+                g, self.row_slot_host[r] = self.row_slot_host[r], -1
+                if g >= 0:
+                    self.slot_refs[g] -= 1
+                    if self.slot_refs[g] == 0:
+                        self.slot_len_host[g] = 0
+                        emptied.append(g)
+            if emptied:
+                self.slot_len.index_fill_(0, torch.tensor(emptied, dtype=torch.int64).to(self.model.device), 0)
 
     def begin(self, generator) -> None:
         """take over the caller's random stream (None = the device's default generator).  A seeded session has no generator of its

@@ -752,12 +752,21 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
     ``row_pos`` (device int32 [B]; event level, head_dim 64; generate_ragged): row b stands at position row_pos[b] of its own
     cache -- RoPE there, K/V stored at that row, attention over rows [0, row_pos[b]] -- and the attention step of every form of the
     layer is the per-row entry point (same launch count).  The positions are always read on the device, eagerly too, so capacity,
-    rope table and kv.len are the caller's business, as with pos_dev.  Not together with ``shared`` or ``pos_dev``."""
+    rope table and kv.len are the caller's business, as with pos_dev.  Not together with ``pos_dev``, nor with the one-prompt form
+    of ``shared``.
+    ``row_pos`` with ``shared`` = (kvs, slot_len, row_slot, workspace) (ops_share.SlotPrefix; DecodeSession(prefix_slots=G)): row b
+    continues the prompt in slot row_slot[b] of ``kvs`` (a KVState of G sequences; slot_len[g] rows of slot g are valid), or none
+    (-1), and ``kv`` holds what lies behind it: cache row j of row b is absolute position pre_b + j.  RoPE at row_pos[b]; the
+    attention step of every form of the layer is the two launches of ops_share.py (attn_prefix_partial_slots,
+    attn_decode_append_rows_shared: +1 launch per layer against the fused per-row form, for every row, sharing or not)."""
     _check_heads(spec)
     B, D = (x_ids.shape[0], x.shape[1]) if x_ids is not None else x.shape
     assert x_ids is None or folded is not None
     H, I, hd = spec.H, spec.I, spec.hd
-    assert row_pos is None or (shared is None and pos_dev is None and spec.kind == "event")
+    from .ops_share import SlotPrefix
+    slots = isinstance(shared, SlotPrefix)
+    assert row_pos is None or ((shared is None or slots) and pos_dev is None and spec.kind == "event")
+    assert not slots or row_pos is not None, "stack_decode: prefix slots go with per-row positions"
     pos = kv.len if pos_dev is None else 0
     attend = None  # what takes the place of the attention step, in all three forms of the layer
     if row_pos is not None:
@@ -767,7 +776,15 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
             else:
                 ops.kv_append_rows(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], B, H, hd, kv.cap, row_pos)
                 ops.attn_decode_rows(qkv, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, spec.scale, row_pos)
-    if shared is not None:
+    if slots:
+        kvs, slot_len, row_slot, ws = shared
+
+        def attend(qkv, o, li):
+            ops.attn_prefix_partial_slots(qkv, rope.cos, rope.sin, kvs.k[li], kvs.v[li], slot_len, row_slot, row_pos, ws, B, H, hd,
+                                          kvs.B, kvs.cap, spec.scale)
+            ops.attn_decode_append_rows_shared(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], ws, o, B, H, hd, kv.cap, kvs.B, kvs.cap,
+                                               spec.scale, slot_len, row_slot, row_pos)
+    elif shared is not None:
         from . import shared as sp
         kvp, pre_len_dev, ws = shared
         assert spec.kind == "event" and kvp.B == 1 and (pre_len_dev is None) == (pos_dev is None)

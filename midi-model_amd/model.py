@@ -814,15 +814,21 @@ class MIDIModel(nn.Module):
                               [disable_control_change], [disable_channels], None if seed is None else [seed])
         return self._ragged_prompts([prompt], rp["max_len"], crop)[0], rp
 
-    def decode_pool(self, rows: int, capacity: int, generator=None, seeded: bool = False):
+    def decode_pool(self, rows: int, capacity: int, generator=None, seeded: bool = False, prefix_slots: int = 0,
+                    prefix_capacity: int = 0):
         """(ours) a ``pool.DecodePool`` on this model: ``rows`` decode rows that requests are admitted into and released from
         while the batch runs (continuous batching).  ``capacity``: cache rows per decode row; a request needs
         max_len + 1 <= capacity (the session's own capacity is rounded up as every session's is, 256 x 2^k).  The pool takes one
         pooled ``row_params`` session at its first admission and holds it until ``close()`` (it is a context manager); it draws
         from ``generator`` as ``generate_ragged`` does.  ``seeded=True``: every request brings a seed of its own
         (``submit(seed=...)``) and the pool draws from no generator (pool.py has the promise and its limits); ``generator`` is
-        then refused.  Nothing is launched here."""
+        then refused.  ``prefix_slots`` = G > 0 with ``prefix_capacity`` = Pmax: the pool's session keeps G prefix slots of Pmax
+        events, and ``submit(..., share_prefix=True)`` stores a prompt of at most Pmax events in one, read ONCE per decoded event
+        for all the rows that continue it -- siblings (``n=k``) and fork children (pool.py).  Nothing is launched
+        here."""
         from .pool import DecodePool
+        if prefix_slots or prefix_capacity:
+            return DecodePool(self, rows, capacity, generator, seeded, prefix_slots, prefix_capacity)
         return DecodePool(self, rows, capacity, generator, seeded)
 
     def generate_pool(self, requests, rows: int, capacity: Optional[int] = None, generator=None) -> list:
@@ -890,8 +896,11 @@ class MIDIModel(nn.Module):
 
     # decode sessions: buffers + captured graphs, one per concurrent generate() call (decode.py)
     def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int, shared_need: int = 0,
-                          ragged: bool = False, row_params: bool = False, seeded: bool = False):
-        """``shared_need`` > 0: a shared-prompt session whose prompt cache holds shared_need events (capacities by the same
+                          ragged: bool = False, row_params: bool = False, seeded: bool = False, prefix_slots: int = 0,
+                          prefix_capacity: int = 0):
+        """``prefix_slots`` / ``prefix_capacity`` (row_params only): a session with that many prefix slots of that many rows
+        (DecodeSession; the capacity is rounded up by the doubling rule too); 0: the session as it was.
+        ``shared_need`` > 0: a shared-prompt session whose prompt cache holds shared_need events (capacities by the same
         doubling rule from 256, so one captured session serves a range of prompt and suffix lengths).  ``ragged``: a session
         with a position per row (generate_ragged), pooled like the others; not together with shared_need.  ``row_params``
         (ragged only): the session that reads temperature, top-p, top-k, masks and limit per row from its own buffers; its key
@@ -906,7 +915,15 @@ class MIDIModel(nn.Module):
             scap = 256
             while scap < shared_need:
                 scap *= 2
-        key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded)
+        pcap = 0
+        if prefix_slots:
+            pcap = 256
+            while pcap < prefix_capacity:
+                pcap *= 2
+        if prefix_slots:
+            key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap)
+        else:
+            key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded)
         pool = self._sessions
         with pool.lock:
             found = None
@@ -919,6 +936,8 @@ class MIDIModel(nn.Module):
         if found is not None:
             found.refresh()  # weights may have been trained / merged since the session derived its folded copies
             return found
+        if prefix_slots:
+            return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap)
         return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded)
 
     def _return_session(self, ses) -> None:

@@ -615,9 +615,14 @@ _POOL = ("kv_store_seqs_rows",)
 _SEEDED = ("sample_top_p_k_seeded", "sample_noise_seeded")
 # ... and the copy of cache sequences inside a live cache, a fork (ops_fork.py; stand-in in tests/emu_fork.py)
 _FORK = ("kv_fork_rows",)
+# ... and decode attention over prefix slots that rows share (ops_share.py; stand-ins in tests/emu_poolshare.py)
+_SHARE = ("attn_prefix_partial_slots", "attn_decode_append_rows_shared")
 
 
 def __getattr__(name: str):
+    if name in _SHARE:
+        from . import ops_share
+        return getattr(ops_share, name)
     if name in _FORK:
         from . import ops_fork
         return getattr(ops_fork, name)

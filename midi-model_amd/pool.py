@@ -61,10 +61,33 @@ limit stated above.  ``n == 1`` without ``hold`` runs exactly what it ran.  Meas
 admitting step takes 5.58 against 10.75 ms at 4000 prompt events, 4.29 against 6.46 ms at 2048, and 3.50 against 3.32 ms at 64 (no
 gain: a short admission is its launches); the copy kernel alone runs at 0.85 to 0.97 of the chip's copy rate at those lengths.
 
+PREFIX SLOTS.  ``model.decode_pool(rows, capacity, prefix_slots=G, prefix_capacity=Pmax)`` runs on a session that keeps
+G prefix slots of Pmax events beside the rows' caches, and ``submit(prompt, ..., share_prefix=True)`` stores the prompt's K/V ONCE, in
+a slot: every row that continues it reads that copy, once per head and event for all of them (``mh_attn_prefix_partial_slots``), and
+its own cache holds only the events behind the prompt (``mh_attn_decode_append_rows_shared``).  With ``n=k`` the k - 1 siblings JOIN
+the leader's slot with no K/V copy at all -- they get the scatter of ``hidden``, position and settings; ``fork`` of a sharing request
+makes children that join its slot and copy only its own events behind the prompt; ``fork`` of any other request is what it was.  A
+slot is counted by the rows that name it, running and held, and is free again when the last of them leaves (``release``, ``drop``,
+``close``).  A sharing group waits at the head of the queue for a free slot as a group waits for rows.  The stated limits:
+  * numerics: the prefix half rounds probabilities to bf16 for its P V product, so a sharing request's ids may differ
+    from the same request unshared -- bit equality with the non-sharing pool is NOT promised for sharing rows;
+  * a seeded pool's promise holds for them as it stands -- "not its row, its neighbours": a sharing request's ids do not depend on how
+    many rows share its slot, on which rows they sit in, or on the other slots, at equal launch shapes (per row the slot kernels are
+    bit-equal to the one-prompt kernels, whatever shares a query tile: tests/test_poolshare_kernels_gpu.py);
+  * cost to the others: every row of a pool with slots pays one more launch per layer and event, sharing or not (measured below);
+  * an admission stores into slots or into rows: sharing leaders and other requests admitted in one ``step()`` take a packed forward
+    each, so a request's admission group is the requests of its own kind admitted with it;
+  * the slot caches come on top of the row caches, which are not shrunk; a prompt must fit ``prefix_capacity`` after the 4096 crop.
+A pool made without ``prefix_slots`` takes the session, the graphs and the launches it took.  Measured (one MI355X,
+``profiles/pool_share_ab.txt``; ``tools/bench_pool_share.py``, tv2o-medium bf16, 64 rows, a group of k siblings alone in
+the pool, median decode step over 64 events): k = 8 behind 4000 events 1.455 against 1.637 ms (1.13 x), 2048: 1.412 against 1.459
+(1.03 x), 512: 1.374 against 1.301 and 64: 1.351 against 1.256 -- sharing LOSES below a prompt of about a thousand events (between
+the measured 512 and 2048), where a step is its launches; k = 4: 1.11 x at 4000, 1.02 x at 2048, the same crossover.  Rows that share
+nothing pay 25 to 45 us a step (2 to 3 %) in a pool with slots.
+
 Out of scope:
   * a background thread or server loop -- the caller owns the loop (and the thread: one pool, one thread);
-  * the shared-prefix ATTENTION of ``generate(share_prompt=True)`` inside the pool: siblings and children share a prompt's prefill,
-    not its K/V -- every row owns a copy and reads it in full at every event;
+  * shrinking the row caches of a pool with prefix slots, or a prompt shared ACROSS pools;
   * a held row's K/V outliving its pool, or moving to another pool: ``close()`` ends every hold;
   * chunking a long admission: a 4096-event prefill on tv2o-medium is 4096 x 0.4 GFLOP of projections (12 layers x 16.8 M
     weights x 2) plus ~0.8 TFLOP of causal attention, about 2.5 TFLOP -- 2.5 to 5 ms at the 500 to 1000 TFLOP/s the block
@@ -95,10 +118,11 @@ _SETTINGS = ("max_len", "temp", "top_p", "top_k", "ban_eos", "disable_patch_chan
 class _Request:
     # (rp["seed"]: a seeded pool's request; prompt: a child's holds its parent's result at the fork; group: the size of the sibling
     #  group this request LEADS in the queue, 0 for the siblings behind it; kw: the settings as given, a child's defaults)
-    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done", "hold", "held", "eos", "group", "kw")
+    #  share: the request continues a prompt that sits in a prefix slot -- a share_prefix submit, its siblings, their fork children)
+    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done", "hold", "held", "eos", "group", "kw", "share")
 
-    def __init__(self, prompt: np.ndarray, rp: dict, kw: dict, hold: bool = False, group: int = 1):
-        self.prompt, self.rp, self.max_len, self.kw = prompt, rp, rp["max_len"][0], kw
+    def __init__(self, prompt: np.ndarray, rp: dict, kw: dict, hold: bool = False, group: int = 1, share: bool = False):
+        self.prompt, self.rp, self.max_len, self.kw, self.share = prompt, rp, rp["max_len"][0], kw, bool(share)
         self.events: List[np.ndarray] = []
         self.row: Optional[int] = None
         self.done = False
@@ -106,11 +130,18 @@ class _Request:
 
 
 class DecodePool:
-    """see the module docstring; made by ``MIDIModel.decode_pool(rows, capacity, generator, seeded)``"""
+    """see the module docstring; made by ``MIDIModel.decode_pool(rows, capacity, generator, seeded, prefix_slots, prefix_capacity)``"""
 
-    def __init__(self, model, rows: int, capacity: int, generator=None, seeded: bool = False):
+    def __init__(self, model, rows: int, capacity: int, generator=None, seeded: bool = False, prefix_slots: int = 0,
+                 prefix_capacity: int = 0):
         if int(rows) != rows or rows < 1 or int(capacity) != capacity or capacity < 2:
             raise ValueError(f"decode_pool: {rows} rows of capacity {capacity}")
+        if (prefix_slots or prefix_capacity) and not (
+                all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in (prefix_slots, prefix_capacity))
+                and prefix_slots >= 1 and prefix_capacity >= 1):
+            raise ValueError(f"decode_pool: prefix_slots={prefix_slots!r}, prefix_capacity={prefix_capacity!r} -- both 0 (no prefix "
+                             "slots), or at least one slot of at least one event")
+        self.prefix_slots, self.prefix_capacity = int(prefix_slots), int(prefix_capacity)
         if seeded and generator is not None:
             raise ValueError("decode_pool: seeded=True together with a generator -- a seeded pool draws nothing from a generator")
         self.model, self.rows, self.capacity, self.generator = model, int(rows), int(capacity), generator
@@ -126,7 +157,7 @@ class DecodePool:
 
     # ---- the caller's side ----------------------------------------------------------------------------------------------
     def submit(self, prompt, max_len=512, temp=1.0, top_p=0.98, top_k=20, ban_eos=False, disable_patch_change=False,
-               disable_control_change=False, disable_channels=None, seed=None, n=1, hold=False):
+               disable_control_change=False, disable_channels=None, seed=None, n=1, hold=False, share_prefix=False):
         """queue one request; -> its id.  Checked as ``generate_ragged`` checks a row with values of its own (the same code, the
         same ``ValueError``s), plus ``max_len + 1 > capacity``; the prompt is cropped to its last 4096 events, as the stream forms
         crop.  ``seed``: required in a seeded pool (an int in [0, 2^64)), refused in an unseeded one.  Nothing is launched here.
@@ -136,9 +167,16 @@ class DecodePool:
         forward, the other n - 1 rows are filled by one ``DecodeSession.fork`` right behind it: one prefill and one K/V copy per
         sibling instead of n prefills.  ``n == 1`` runs exactly what it ran, and its id is a plain int.
         ``hold``: when the request finishes by reaching ``max_len`` its row is kept (``held()``, ``fork()``, ``drop()``); one that
-        ends on EOS is released as usual."""
+        ends on EOS is released as usual.
+        ``share_prefix`` (a pool made with ``prefix_slots``): the prompt's K/V is stored ONCE, in a prefix slot, and every row that
+        continues it reads that copy -- the request itself, its ``n - 1`` siblings, which then join the slot with no K/V copy at
+        all, and their fork children.  The request waits at the head of the queue for a free slot as a group waits for rows.
+        ``ValueError``, before any launch: a pool without slots; a prompt of more than ``prefix_capacity`` events (after the crop)."""
         if self._closed:
             raise ValueError("DecodePool.submit: the pool is closed")
+        if share_prefix and not self.prefix_slots:
+            raise ValueError("DecodePool.submit: share_prefix needs a pool with prefix slots -- decode_pool(..., prefix_slots=G, "
+                             "prefix_capacity=Pmax)")
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= self.rows:
             raise ValueError(f"DecodePool.submit: n = {n!r} is not an integer in [1, {self.rows}] (the pool's rows)")
         n = int(n)
@@ -146,11 +184,14 @@ class DecodePool:
         kw = dict(zip(_SETTINGS, (max_len, temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change,
                                   disable_channels)))
         checked = [self._checked(prompt, kw, s, "submit") for s in seeds]
+        if share_prefix and len(checked[0][0]) > self.prefix_capacity:
+            raise ValueError(f"DecodePool.submit: share_prefix with a prompt of {len(checked[0][0])} events in a pool whose prefix "
+                             f"slots hold {self.prefix_capacity}")
         rids = []
         for i, (p, rp) in enumerate(checked):
             rids.append(self._next_id)
             self._next_id += 1
-            self.requests[rids[-1]] = _Request(p, rp, kw, hold=hold, group=n if i == 0 else 0)
+            self.requests[rids[-1]] = _Request(p, rp, kw, hold=hold, group=n if i == 0 else 0, share=share_prefix)
             self.queue.append(rids[-1])
         return rids[0] if n == 1 else rids
 
@@ -203,9 +244,11 @@ class DecodePool:
         (inherited events in front of their own in ``result()``), their first event is reported by the next ``step()``; -> their
         ids.  The parent is running or held (``submit(hold=True)``); it runs on, or stays held, untouched.  No prefill: the
         parent's K/V is copied into ``count`` free rows and the rows' state set in one ``DecodeSession.fork`` -- one kernel launch
-        and the scatter of an admission.  The rows are taken NOW, the lowest first and ahead of the queue.  A setting left at None
-        is the parent's; ``max_len`` must exceed ``len(result(rid))`` (so a held parent's children need one).  In a seeded pool
-        ``seed`` is an int for one child, a sequence of ``count`` ints for several.
+        and the scatter of an admission.  The children of a parent that shares its prompt (``share_prefix``) JOIN its prefix slot:
+        only the parent's own events behind the prompt are copied, and they are share requests themselves.  The rows are taken NOW,
+        the lowest first and ahead of the queue.  A setting left at None is the parent's; ``max_len`` must exceed
+        ``len(result(rid))`` (so a held parent's children need one).  In a seeded pool ``seed`` is an int for one child, a sequence
+        of ``count`` ints for several.
         Seeded pools: the variate counter of an event is its index in the result, so a child continues the parent's counter under
         its own seed -- a child given the parent's seed and settings repeats the parent event for event, and a held request forked
         under its own seed with a larger ``max_len`` gives exactly what an uninterrupted request with that ``max_len`` gives.  The
@@ -237,14 +280,15 @@ class DecodePool:
         rp = {name: [c[1][name][0] for c in checked] for name in checked[0][1]}
         first, ban = self.model._mask_rows(rp)
         with torch.inference_mode():
+            join = {"join": [True] * count} if r.share else {}
             self.ses.fork([r.row] * count, rows, [len(prompt)] * count, rp["max_len"], rp["temp"], rp["top_p"], rp["top_k"],
-                          first, ban, seeds=rp.get("seed"), from_held=[r.held] * count)
+                          first, ban, seeds=rp.get("seed"), from_held=[r.held] * count, **join)
         del self.free[:count]
         rids = []
         for row, (p, one) in zip(rows, checked):
             rids.append(self._next_id)
             self._next_id += 1
-            child = self.requests[rids[-1]] = _Request(p, one, kw, hold=hold)
+            child = self.requests[rids[-1]] = _Request(p, one, kw, hold=hold, share=r.share)
             child.row = row
             self.occupied[row] = rids[-1]
         return rids
@@ -270,6 +314,9 @@ class DecodePool:
         self._closed = True
         if self.ses is not None:
             ses, self.ses = self.ses, None
+            if self.prefix_slots:  # every row leaves its slot and every slot is emptied: nothing outlives the pool
+                with torch.inference_mode():
+                    ses.reset()
             ses.end()
             self.model._return_session(ses)
 
@@ -284,8 +331,9 @@ class DecodePool:
     def _session(self):
         if self.ses is None:
             # (1.0, 0.98, 1 fill a NEW session's buffers through its warm-up pass; every admission overwrites its rows')
+            slots = dict(prefix_slots=self.prefix_slots, prefix_capacity=self.prefix_capacity) if self.prefix_slots else {}
             ses = self.model._checkout_session(self.rows, self.capacity, 1.0, 0.98, 1, ragged=True, row_params=True,
-                                                seeded=self.seeded)
+                                                seeded=self.seeded, **slots)
             ses.reset()                      # every row free: pos = pos_limit = 0
             ses.begin(self.generator)
             self.ses = ses
@@ -294,39 +342,60 @@ class DecodePool:
     def _admit_queued(self) -> None:
         # FIFO, whole sibling groups: the request at the head leads a group of r.group rows (1: a lone request); a group that
         # does not fit waits there, and what is queued behind it waits with it
-        groups, k = [], 0
+        # (a share_prefix group needs a free prefix slot as well, and waits in the same place for one)
+        groups, k, slots = [], 0, self._free_slots()
         while self.queue and k + self.requests[self.queue[0]].group <= len(self.free):
-            g = self.requests[self.queue[0]].group
+            head = self.requests[self.queue[0]]
+            if head.share and not slots:
+                break
+            g = head.group
             groups.append([self.queue.popleft() for _ in range(g)])
             k += g
+            if head.share:
+                slots.pop(0)
         if k == 0:
             return
         taken = self.free[:k]
         del self.free[:k]
-        rows, rids, forks, at = [], [], [], 0   # the leaders and their rows; (leader's row, sibling's row, sibling's id)
+        lead = {True: [], False: []}  # share -> [(row, request id)] of the group leaders
+        forks, at = [], 0             # (leader's row, sibling's row, sibling's id, the sibling joins the leader's slot)
         for grp in groups:
-            rows.append(taken[at])
-            rids.append(grp[0])
-            forks += [(taken[at], taken[at + i], rid) for i, rid in enumerate(grp) if i > 0]
+            share = self.requests[grp[0]].share
+            lead[share].append((taken[at], grp[0]))
+            forks += [(taken[at], taken[at + i], rid, share) for i, rid in enumerate(grp) if i > 0]
             at += len(grp)
-        reqs = [self.requests[rid] for rid in rids]
-        rp = {name: [r.rp[name][0] for r in reqs] for name in reqs[0].rp}
-        first, ban = self.model._mask_rows(rp)
-        tokens = torch.from_numpy(np.concatenate([r.prompt for r in reqs], axis=0))
-        self._session().admit(rows, tokens, [len(r.prompt) for r in reqs], rp["max_len"], rp["temp"], rp["top_p"], rp["top_k"],
-                              first, ban, seeds=rp.get("seed"))
-        for row, rid, r in zip(rows, rids, reqs):
-            r.row = row
-            self.occupied[row] = rid
-        if forks:  # the siblings: the leaders' K/V and last hidden rows, right behind the prefill that made them
-            sibs = [self.requests[rid] for _, _, rid in forks]
-            rp = {name: [r.rp[name][0] for r in sibs] for name in sibs[0].rp}
+        ses = self._session()
+        # an admission stores into slots or into rows: the sharing leaders take a packed forward of their own, K/V into free slots
+        for share in (True, False):
+            if not lead[share]:
+                continue
+            rows, rids = [r for r, _ in lead[share]], [i for _, i in lead[share]]
+            reqs = [self.requests[rid] for rid in rids]
+            rp = {name: [r.rp[name][0] for r in reqs] for name in reqs[0].rp}
             first, ban = self.model._mask_rows(rp)
-            self.ses.fork([s for s, _, _ in forks], [d for _, d, _ in forks], [len(r.prompt) for r in sibs], rp["max_len"],
-                          rp["temp"], rp["top_p"], rp["top_k"], first, ban, seeds=rp.get("seed"))
-            for (_, row, rid), r in zip(forks, sibs):
+            tokens = torch.from_numpy(np.concatenate([r.prompt for r in reqs], axis=0))
+            into = {"slots": ses.free_slots()[:len(rows)]} if share else {}
+            ses.admit(rows, tokens, [len(r.prompt) for r in reqs], rp["max_len"], rp["temp"], rp["top_p"], rp["top_k"], first, ban,
+                      seeds=rp.get("seed"), **into)
+            for row, rid, r in zip(rows, rids, reqs):
                 r.row = row
                 self.occupied[row] = rid
+        if forks:  # the siblings, right behind the prefills that made their leaders: the leaders' K/V and last hidden rows -- a
+            #        sharing group's siblings JOIN the leader's slot instead and copy nothing
+            sibs = [self.requests[rid] for _, _, rid, _ in forks]
+            rp = {name: [r.rp[name][0] for r in sibs] for name in sibs[0].rp}
+            first, ban = self.model._mask_rows(rp)
+            join = {"join": [j for _, _, _, j in forks]} if any(j for _, _, _, j in forks) else {}
+            ses.fork([s for s, _, _, _ in forks], [d for _, d, _, _ in forks], [len(r.prompt) for r in sibs], rp["max_len"],
+                     rp["temp"], rp["top_p"], rp["top_k"], first, ban, seeds=rp.get("seed"), **join)
+            for (_, row, rid, _), r in zip(forks, sibs):
+                r.row = row
+                self.occupied[row] = rid
+
+    def _free_slots(self) -> List[int]:
+        if self.ses is None:
+            return list(range(self.prefix_slots))
+        return self.ses.free_slots()
 
     def step(self) -> List[Tuple[int, np.ndarray, bool]]:
         """admit what fits, sample one event for every row, -> [(request id, event np.int64 (8,), done)] for the occupied rows,
@@ -340,8 +409,10 @@ class DecodePool:
         with torch.inference_mode():
             self._admit_queued()
             if not self.occupied:  # (a sibling group at the head of the queue, and held requests on the rows it waits for)
-                raise RuntimeError(f"DecodePool.step: nothing runs and the group of {self.requests[self.queue[0]].group} requests "
-                                   f"at the head of the queue cannot be admitted: {len(self.free)} rows are free, "
+                head = self.requests[self.queue[0]]
+                slots = f", {len(self._free_slots())} of {self.prefix_slots} prefix slots (it needs one)" if head.share else ""
+                raise RuntimeError(f"DecodePool.step: nothing runs and the group of {head.group} requests "
+                                   f"at the head of the queue cannot be admitted: {len(self.free)} rows are free{slots}, "
                                    f"{len(self.held_rows)} held -- drop() a held request")
             ses = self.ses
             live = [row in self.occupied for row in range(self.rows)]
