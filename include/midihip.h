@@ -519,6 +519,26 @@ int mh_kv_store_seqs_rows(const void* qkv, const int32_t* seq_start, const int32
 int mh_kv_fork_rows(void* kcache, void* vcache, const int32_t* src, const int32_t* dst, const int32_t* len, int64_t n,
                     int64_t max_len, int64_t layers, int64_t B, int H, int hd, int64_t Lmax, int dtype, void* stream);
 
+/* ---- the event-level K/V cache in 8 bits (attention_kvq.hip; DecodeSession(kv_dtype="fp8")) -----------------
+ * Per layer: k8, v8 uint8 [B, H, Lmax, 64] hold OCP e4m3fn codes, sc fp32 [B, H, Lmax, 2] the (K scale, V scale) of every
+ * (sequence, head, event).  Q(x) of a 64-element bf16 row: amax = max |x_e|, s = amax / 448 as an IEEE fp32 division (s = 1 for an
+ * all-zero row), code_e = e4m3fn(clamp(x_e / s, -448, 448)) rounded to nearest even with subnormals kept; D(code, s)_e =
+ * float(code_e) * s.  The NaN codes 0x7F / 0xFF are never produced.  bf16 activations and head_dim 64 only (MH_ERR_ARG otherwise).
+ *   mh_kv_store_seqs_rows_fp8: mh_kv_store_seqs_rows with Q() of every K row (as qkv holds it: rotated) and V row written as codes
+ *     plus the scale pair; the same dropped-row rules and host checks.
+ *   mh_attn_decode_append_rows_fp8: mh_attn_decode_append_rows over this cache.  The new position's k row is rotated and rounded to
+ *     bf16 as there, Q() of it and of the v row goes to cache row row_pos[b], and the block attends over cached rows [0, row_pos[b])
+ *     plus the new row in its DEQUANTIZED form: score_j = (sum_e q_e float(kcode_je)) ks_j, acc_e += (p_j vs_j) float(vcode_je).
+ *   mh_kv_fork_rows_fp8: mh_kv_fork_rows over whole cache tensors k8, v8 [layers, B, H, Lmax, 64] and sc [layers, B, H, Lmax, 2]:
+ *     codes and scale pairs of positions [0, len[p]) copied bit for bit; the same dropped-pair rules and host checks.        */
+int mh_kv_store_seqs_rows_fp8(const void* qkv, const int32_t* seq_start, const int32_t* rows, void* k8, void* v8, float* sc,
+                              int64_t n, int64_t B, int64_t M, int H, int hd, int64_t Lmax, int dtype, void* stream);
+int mh_attn_decode_append_rows_fp8(const void* qkv, const float* cos_t, const float* sin_t, void* k8, void* v8, float* sc, void* o,
+                                   int64_t B, int H, int hd, int64_t Lmax, float scale, const int32_t* row_pos, int dtype,
+                                   void* stream);
+int mh_kv_fork_rows_fp8(void* k8, void* v8, float* sc, const int32_t* src, const int32_t* dst, const int32_t* len, int64_t n,
+                        int64_t max_len, int64_t layers, int64_t B, int H, int hd, int64_t Lmax, void* stream);
+
 /* ---- grammar-masked softmax for the sampler (midi_model.py:202-223) -----------------------------------------
  * probs[b,:] = softmax(logits[b,:]/temp) * mask_b, mask_b = ids in [lo[b],hi[b]) or, when lo[b] < 0, the
  * `first_mask` table (event ids + EOS).  fp32 output, as torch.softmax on fp32 logits gives.              */

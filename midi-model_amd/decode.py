@@ -95,6 +95,14 @@ G, Pmax) only: nothing is recaptured.  ``admit(slots=...)`` stores the admitted 
 when that is empty; ``release`` frees a slot (slot_len = 0, in stream order) when its last row leaves, a held row keeping its slot.
 The host keeps the slot of every row, every slot's length and its reference count (``slot_refs``): it decides which slot is free.
 ``prefix_slots=0`` is the session as it was: no new buffer, no new key, the same launches.
+
+``kv_dtype="fp8"`` (row_params sessions, seeded or not; a bf16 model, at most 256 rows; decode_pool(kv_dtype="fp8")):
+``kv1`` is an ``engine.KVStateQ`` -- e4m3fn codes with an fp32 scale per (row, head, event) for K and for V, 136 bytes where the
+bf16 cache holds 256.  ``admit`` stores through mh_kv_store_seqs_rows_fp8, the net step attends through
+mh_attn_decode_append_rows_fp8 (the new row is quantized first and attended to as the cache holds it, so a fork or a
+held-then-forked request sees the keys an uninterrupted one saw) and ``fork`` copies through mh_kv_fork_rows_fp8.  The graphs are
+captured from the same schedule and nothing is recaptured.  Not with prefix slots or a shared prompt; ``prefill`` and
+``prefill_ragged`` refuse such a session.  ``kv_dtype=None`` is the session as it was: the same key, buffers and launches.
 """
 from __future__ import annotations
 
@@ -106,7 +114,7 @@ import numpy as np
 import torch
 
 from . import engine, ops
-from .engine import KVState, RopeTable
+from .engine import KVState, KVStateQ, RopeTable
 
 
 # One capture at a time per process, and in thread-local error mode: generators of other threads (app.py runs up to 10 on
@@ -128,7 +136,7 @@ def graphs_enabled(device: torch.device) -> bool:
 class DecodeSession:
     def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int, shared_capacity: int = 0,
                  ragged: bool = False, row_params: bool = False, seeded: bool = False, prefix_slots: int = 0,
-                 prefix_capacity: int = 0):
+                 prefix_capacity: int = 0, kv_dtype: Optional[str] = None):
         tok = model.tokenizer
         self.model, self.B, self.cap, self.temp = model, B, capacity, float(temp)
         self.top_p, self.top_k = float(top_p), int(top_k)
@@ -137,12 +145,16 @@ class DecodeSession:
         self.row_params = bool(row_params)
         self.seeded = bool(seeded)
         self.prefix_slots, self.prefix_capacity = int(prefix_slots), int(prefix_capacity)
+        self.kv_dtype = kv_dtype
         self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params, seeded,
-                                 prefix_slots, prefix_capacity)
+                                 prefix_slots, prefix_capacity, kv_dtype)
         dev, dt = model.device, model.dtype
         self.T, self.V, self.Vp = tok.max_token_seq, tok.vocab_size, model.vocab_padded
         spec, tspec = model._specs["net"], model._specs["net_token"]
-        self.kv1 = KVState(spec, B, capacity, model._flat)  # (shared: the generated suffix only)
+        if kv_dtype == "fp8":  # codes and a scale pair per (row, head, event); never grown
+            self.kv1 = KVStateQ(spec, B, capacity, model._flat)
+        else:
+            self.kv1 = KVState(spec, B, capacity, model._flat)  # (shared: the generated suffix only)
         self.kv2 = KVState(tspec, B, self.T, model._flat)
         self.kvp = self.pre_len = self.ws = None
         if self.shared_capacity > 0:
@@ -231,7 +243,19 @@ class DecodeSession:
 
     @staticmethod
     def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False, row_params=False, seeded=False,
-                 prefix_slots=0, prefix_capacity=0):
+                 prefix_slots=0, prefix_capacity=0, kv_dtype=None):
+        if kv_dtype is not None:
+            if kv_dtype != "fp8":
+                raise ValueError(f"DecodeSession: kv_dtype={kv_dtype!r} -- None (the cache in the model's dtype) or \"fp8\"")
+            if not (ragged and row_params):
+                raise ValueError("DecodeSession: kv_dtype=\"fp8\" is a form of the per-row session -- it needs ragged=True, "
+                                 "row_params=True")
+            if prefix_slots or prefix_capacity or shared_capacity:
+                raise ValueError("DecodeSession: kv_dtype=\"fp8\" is not available with prefix slots or a shared prompt (their "
+                                 "caches and kernels are bf16)")
+            if model._flat.dtype != torch.bfloat16 or B > 256:
+                raise ValueError(f"DecodeSession: kv_dtype=\"fp8\" needs a bf16 model and at most 256 rows (the fused per-row "
+                                 f"attention is the one form that reads the fp8 cache): {model._flat.dtype}, {B} rows")
         if prefix_slots or prefix_capacity:
             if not (ragged and row_params) or int(prefix_slots) != prefix_slots or int(prefix_capacity) != prefix_capacity \
                     or prefix_slots < 1 or prefix_capacity < 1:
@@ -250,6 +274,8 @@ class DecodeSession:
             form = ("ragged", "row_params", "seeded") if seeded else ("ragged", "row_params")
             if prefix_slots:  # (no existing key changes: a session without slots keeps the key it had)
                 form += (("slots", int(prefix_slots), int(prefix_capacity)),)
+            if kv_dtype is not None:  # (likewise: only an fp8 session carries it)
+                form += (("kv", "fp8"),)
             return (model._flat.data_ptr(), model._flat.dtype, B, capacity, form)
         key = (model._flat.data_ptr(), model._flat.dtype, B, capacity, float(temp), float(top_p), int(top_k))
         if ragged:
@@ -451,6 +477,8 @@ class DecodeSession:
         """tokens [B, S, T]: causal forward over the prompt from an empty cache; leaves hidden = last position.
         A shared session runs ROW 0 alone (the caller has checked that the rows are equal) into ``kvp`` and hands its last hidden
         row to all B rows; the suffix cache starts empty."""
+        if self.kv_dtype is not None:
+            raise ValueError("DecodeSession.prefill: an fp8-cache session is filled by admit() alone")
         m = self.model
         spec = m._specs["net"]
         B, S, T = tokens.shape
@@ -526,6 +554,8 @@ class DecodeSession:
         """tokens [M, T]: the B prompts laid end to end, prompt b of lengths[b] events.  One packed causal forward from empty
         caches (engine.stack_prefill_seqs); leaves hidden[b] = prompt b's last position and pos[b] = lengths[b].  Prompts of one
         length take prefill()'s uniform forward instead, so that generate_ragged continues them exactly as generate() does."""
+        if self.kv_dtype is not None:
+            raise ValueError("DecodeSession.prefill_ragged: an fp8-cache session is filled by admit() alone")
         m = self.model
         spec = m._specs["net"]
         lengths = [int(n) for n in lengths]
@@ -757,7 +787,9 @@ class DecodeSession:
         seed_dev = more_dev[:1] if self.seeded else []
         pairs = pairs.view(3, n)
         # ---- the K/V of every layer, one launch
-        if copies is None:
+        if self.kv_dtype is not None:  # (no prefix slots with it: every pair copies lengths[p] rows) codes and scale pairs
+            ops.kv_fork_rows_fp8(self.kv1.k8, self.kv1.v8, self.kv1.sc, src, dst, lengths, dev=pairs)
+        elif copies is None:
             ops.kv_fork_rows(self.kv1.k, self.kv1.v, src, dst, lengths, dev=pairs)
         elif copies:
             ops.kv_fork_rows(self.kv1.k, self.kv1.v, *([c[k] for c in copies] for k in range(3)),

@@ -623,9 +623,36 @@ class KVState:
         self.cap = cap
 
 
+class KVStateQ:
+    """The event-level cache in 8 bits (DecodeSession(kv_dtype="fp8"); attention_kvq.hip): per layer ``k8`` / ``v8``
+    uint8 [B, H, cap, 64] hold e4m3fn codes and ``sc`` float32 [B, H, cap, 2] the (K scale, V scale) of every (row, head, event) --
+    136 bytes per head and event where KVState holds 256.  Never grown: a captured graph holds its addresses.  Served by
+    stack_prefill_seqs(rows=...) and by the fused per-row attention of stack_decode(row_pos=...) alone; every other form refuses it."""
+
+    def __init__(self, spec: StackSpec, B: int, capacity: int, like: torch.Tensor):
+        if spec.kind != "event" or spec.hd != 64 or like.dtype != torch.bfloat16:
+            raise ValueError(f"KVStateQ: the fp8 cache serves the event-level stack (head_dim 64) of a bf16 model: {spec.kind}, "
+                             f"head_dim {spec.hd}, {like.dtype}")
+        self.spec, self.B, self.cap, self.len = spec, B, capacity, 0
+        shape = (spec.L, B, spec.H, capacity)
+        self.k8 = torch.empty(shape + (spec.hd,), dtype=torch.uint8, device=like.device)
+        self.v8 = torch.empty(shape + (spec.hd,), dtype=torch.uint8, device=like.device)
+        self.sc = torch.empty(shape + (2,), dtype=torch.float32, device=like.device)
+
+    def nbytes(self) -> int:
+        return self.k8.numel() + self.v8.numel() + 4 * self.sc.numel()
+
+
+def _refuse_kvq(kv, what: str) -> None:
+    if isinstance(kv, KVStateQ):
+        raise ValueError(f"{what}: the fp8 K/V cache is served by stack_prefill_seqs(rows=...) and the fused per-row attention of "
+                         "stack_decode(row_pos=...) only")
+
+
 def stack_prefill(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, slen: int, rope: RopeTable, kv: KVState,
                   folded=None):
     """Causal forward over a whole prompt from an EMPTY cache, storing K/V rows [0, slen)."""
+    _refuse_kvq(kv, "stack_prefill")
     assert kv.len == 0
     kv.reserve(slen)
     qkvs: list = []
@@ -644,8 +671,14 @@ def stack_prefill_seqs(spec: StackSpec, W: StackTensors, x: torch.Tensor, plan, 
     (a ragged decode session: ``pos`` on the device).
     ``rows`` (DecodeSession.admit; a sequence of plan.n distinct ints inside [0, kv.B), ``rows_dev`` its int32 device copy):
     sequence s fills rows [0, L_s) of cache sequence rows[s] of a cache that is IN USE -- kv.B may exceed plan.n, the cache is not
-    grown (a captured graph holds its address), and the other sequences are not touched: one kv_store_seqs_rows launch per layer."""
+    grown (a captured graph holds its address), and the other sequences are not touched: one kv_store_seqs_rows launch per layer.
+    ``kv`` a ``KVStateQ`` (``rows`` only, bf16): that launch is kv_store_seqs_rows_fp8, which quantizes what it stores."""
     assert plan.M == x.shape[0]
+    quant = isinstance(kv, KVStateQ)  # the fp8 cache: the store quantizes (one mh_kv_store_seqs_rows_fp8 per layer)
+    if quant and rows is None:
+        _refuse_kvq(kv, "stack_prefill_seqs without rows")
+    if quant and x.dtype != torch.bfloat16:
+        raise ValueError(f"stack_prefill_seqs: the fp8 K/V cache takes bf16 activations, not {x.dtype}")
     if rows is None:
         assert kv.B == plan.n
         kv.reserve(plan.max_len)
@@ -656,7 +689,9 @@ def stack_prefill_seqs(spec: StackSpec, W: StackTensors, x: torch.Tensor, plan, 
     qkvs: list = []
     y, _ = stack_forward(spec, W, x, 1, plan.M, rope, save=False, kv_out=qkvs, folded=folded, seqs=plan)
     for li, qkv in enumerate(qkvs):
-        if rows is None:
+        if quant:
+            ops.kv_store_seqs_rows_fp8(qkv, plan, rows, kv.k8[li], kv.v8[li], kv.sc[li], spec.H, spec.hd, kv.cap, rows_dev=rows_dev)
+        elif rows is None:
             ops.kv_store_seqs(qkv, plan, kv.k[li], kv.v[li], spec.H, spec.hd, kv.cap)
         else:
             ops.kv_store_seqs_rows(qkv, plan, rows, kv.k[li], kv.v[li], spec.H, spec.hd, kv.cap, rows_dev=rows_dev)
@@ -672,6 +707,7 @@ def stack_extend(spec: StackSpec, W: StackTensors, x: torch.Tensor, nseq: int, s
     block, K/V store and gather, two torch copies: the chunk's rows into the gathered buffer and its outputs out of the
     attention's) whatever ``slen`` is (the event-by-event form this replaces took 5 x slen).  Event-level stack (heads of 64)."""
     _check_heads(spec)
+    _refuse_kvq(kv, "stack_extend")
     assert spec.kind == "event"
     M, D = x.shape
     assert M == nseq * slen
@@ -758,18 +794,27 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
     continues the prompt in slot row_slot[b] of ``kvs`` (a KVState of G sequences; slot_len[g] rows of slot g are valid), or none
     (-1), and ``kv`` holds what lies behind it: cache row j of row b is absolute position pre_b + j.  RoPE at row_pos[b]; the
     attention step of every form of the layer is the two launches of ops_share.py (attn_prefix_partial_slots,
-    attn_decode_append_rows_shared: +1 launch per layer against the fused per-row form, for every row, sharing or not)."""
+    attn_decode_append_rows_shared: +1 launch per layer against the fused per-row form, for every row, sharing or not).
+    ``kv`` a ``KVStateQ`` (DecodeSession(kv_dtype="fp8")): ``row_pos`` without ``shared`` in the fused layer forms only (bf16, at most
+    256 rows) -- the attention step is mh_attn_decode_append_rows_fp8, same launch count; ``ValueError`` before any launch otherwise."""
     _check_heads(spec)
     B, D = (x_ids.shape[0], x.shape[1]) if x_ids is not None else x.shape
     assert x_ids is None or folded is not None
     H, I, hd = spec.H, spec.I, spec.hd
+    quant = isinstance(kv, KVStateQ)
+    if quant and (row_pos is None or shared is not None):
+        _refuse_kvq(kv, "stack_decode without row_pos" if row_pos is None else "stack_decode(shared=...)")
     from .ops_share import SlotPrefix
     slots = isinstance(shared, SlotPrefix)
     assert row_pos is None or ((shared is None or slots) and pos_dev is None and spec.kind == "event")
     assert not slots or row_pos is not None, "stack_decode: prefix slots go with per-row positions"
     pos = kv.len if pos_dev is None else 0
     attend = None  # what takes the place of the attention step, in all three forms of the layer
-    if row_pos is not None:
+    if quant:  # (checked below: only the fused layer forms get here)
+        def attend(qkv, o, li):
+            ops.attn_decode_append_rows_fp8(qkv, rope.cos, rope.sin, kv.k8[li], kv.v8[li], kv.sc[li], o, B, H, hd, kv.cap, spec.scale,
+                                            row_pos)
+    elif row_pos is not None:
         def attend(qkv, o, li):
             if fused:
                 ops.attn_decode_append_rows(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, spec.scale, row_pos)
@@ -807,6 +852,9 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
     assert x_ids is None or use_wide or B <= 64, "stack_decode: x_ids with a row count no skinny entry point serves"
     fused = (x_ids is not None) or use_wide or (ops.skinny_ok(x, D) and ops.skinny_ok(x, I))
     skinny = ops.gemm_skinny_wide if use_wide else ops.gemm_skinny  # one entry point per row-count class, same arguments
+    if quant and not (fused and x.dtype == torch.bfloat16):
+        raise ValueError(f"stack_decode: the fp8 K/V cache is served by the fused per-row attention only (bf16, at most 256 rows), "
+                         f"not by the unfused kv_append_rows + attn_decode_rows pair: {B} rows of {x.dtype}")
     for li, lw in enumerate(W.layers):
         if fused and folded is not None:
             wqkv_n, wgu_n = folded[li]

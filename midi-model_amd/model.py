@@ -815,7 +815,7 @@ class MIDIModel(nn.Module):
         return self._ragged_prompts([prompt], rp["max_len"], crop)[0], rp
 
     def decode_pool(self, rows: int, capacity: int, generator=None, seeded: bool = False, prefix_slots: int = 0,
-                    prefix_capacity: int = 0):
+                    prefix_capacity: int = 0, kv_dtype: Optional[str] = None):
         """(ours) a ``pool.DecodePool`` on this model: ``rows`` decode rows that requests are admitted into and released from
         while the batch runs (continuous batching).  ``capacity``: cache rows per decode row; a request needs
         max_len + 1 <= capacity (the session's own capacity is rounded up as every session's is, 256 x 2^k).  The pool takes one
@@ -824,20 +824,25 @@ class MIDIModel(nn.Module):
         (``submit(seed=...)``) and the pool draws from no generator (pool.py has the promise and its limits); ``generator`` is
         then refused.  ``prefix_slots`` = G > 0 with ``prefix_capacity`` = Pmax: the pool's session keeps G prefix slots of Pmax
         events, and ``submit(..., share_prefix=True)`` stores a prompt of at most Pmax events in one, read ONCE per decoded event
-        for all the rows that continue it -- siblings (``n=k``) and fork children (pool.py).  Nothing is launched
-        here."""
+        for all the rows that continue it -- siblings (``n=k``) and fork children (pool.py).
+        ``kv_dtype="fp8"``: the rows' event-level K/V is cached as e4m3 codes with a scale per head and event, 0.53 x the bytes
+        (pool.py "FP8 K/V"); a bf16 model, at most 256 rows, not with prefix slots (``ValueError``).  Nothing is
+        launched here."""
         from .pool import DecodePool
+        if kv_dtype is not None:
+            return DecodePool(self, rows, capacity, generator, seeded, prefix_slots, prefix_capacity, kv_dtype=kv_dtype)
         if prefix_slots or prefix_capacity:
             return DecodePool(self, rows, capacity, generator, seeded, prefix_slots, prefix_capacity)
         return DecodePool(self, rows, capacity, generator, seeded)
 
-    def generate_pool(self, requests, rows: int, capacity: Optional[int] = None, generator=None) -> list:
+    def generate_pool(self, requests, rows: int, capacity: Optional[int] = None, generator=None,
+                      kv_dtype: Optional[str] = None) -> list:
         """(ours) ``requests``: a list of dicts, each the keyword arguments of ``DecodePool.submit`` (``prompt`` and any of max_len,
         temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change, disable_channels, seed).  If EVERY request
         carries ``"seed"`` the pool is a seeded one; some with and some without is a ``ValueError``.  They are submitted in order
         to one pool of ``rows`` rows and stepped until all are done: a request waits only until a row is free, and a row that
         finishes is handed to the next request at once.  -> a list of ``np.ndarray (<= max_len, 8) int64``, request i's at index
-        i, its prompt in front.  ``capacity`` defaults to the largest max_len + 1."""
+        i, its prompt in front.  ``capacity`` defaults to the largest max_len + 1.  ``kv_dtype``: as ``decode_pool`` takes it."""
         requests = list(requests)
         if not requests:
             return []
@@ -846,7 +851,8 @@ class MIDIModel(nn.Module):
         with_seed = sum("seed" in r and r["seed"] is not None for r in requests)
         if with_seed not in (0, len(requests)):
             raise ValueError(f"generate_pool: {with_seed} of {len(requests)} requests carry a seed -- all of them or none")
-        with self.decode_pool(rows, capacity, generator, seeded=with_seed > 0) as pool:
+        kvq = dict(kv_dtype=kv_dtype) if kv_dtype is not None else {}
+        with self.decode_pool(rows, capacity, generator, seeded=with_seed > 0, **kvq) as pool:
             ids = [pool.submit(**r) for r in requests]
             while pool.pending():
                 pool.step()
@@ -897,8 +903,10 @@ class MIDIModel(nn.Module):
     # decode sessions: buffers + captured graphs, one per concurrent generate() call (decode.py)
     def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int, shared_need: int = 0,
                           ragged: bool = False, row_params: bool = False, seeded: bool = False, prefix_slots: int = 0,
-                          prefix_capacity: int = 0):
-        """``prefix_slots`` / ``prefix_capacity`` (row_params only): a session with that many prefix slots of that many rows
+                          prefix_capacity: int = 0, kv_dtype: Optional[str] = None):
+        """``kv_dtype`` = "fp8" (row_params only): the session whose event-level cache holds e4m3 codes and scales (DecodeSession); a
+        pooled session of its own kind, None: the session as it was.
+        ``prefix_slots`` / ``prefix_capacity`` (row_params only): a session with that many prefix slots of that many rows
         (DecodeSession; the capacity is rounded up by the doubling rule too); 0: the session as it was.
         ``shared_need`` > 0: a shared-prompt session whose prompt cache holds shared_need events (capacities by the same
         doubling rule from 256, so one captured session serves a range of prompt and suffix lengths).  ``ragged``: a session
@@ -920,7 +928,10 @@ class MIDIModel(nn.Module):
             pcap = 256
             while pcap < prefix_capacity:
                 pcap *= 2
-        if prefix_slots:
+        if kv_dtype is not None:
+            key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap,
+                                         kv_dtype)
+        elif prefix_slots:
             key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap)
         else:
             key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded)
@@ -936,6 +947,8 @@ class MIDIModel(nn.Module):
         if found is not None:
             found.refresh()  # weights may have been trained / merged since the session derived its folded copies
             return found
+        if kv_dtype is not None:
+            return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap, kv_dtype)
         if prefix_slots:
             return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap)
         return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded)

@@ -617,9 +617,14 @@ _SEEDED = ("sample_top_p_k_seeded", "sample_noise_seeded")
 _FORK = ("kv_fork_rows",)
 # ... and decode attention over prefix slots that rows share (ops_share.py; stand-ins in tests/emu_poolshare.py)
 _SHARE = ("attn_prefix_partial_slots", "attn_decode_append_rows_shared")
+# ... and the store, decode attention and fork over the 8-bit K/V cache (ops_kvq.py; stand-ins in tests/emu_kvq.py)
+_KVQ = ("kv_store_seqs_rows_fp8", "attn_decode_append_rows_fp8", "kv_fork_rows_fp8")
 
 
 def __getattr__(name: str):
+    if name in _KVQ:
+        from . import ops_kvq
+        return getattr(ops_kvq, name)
     if name in _SHARE:
         from . import ops_share
         return getattr(ops_share, name)

@@ -85,6 +85,25 @@ the pool, median decode step over 64 events): k = 8 behind 4000 events 1.455 aga
 the measured 512 and 2048), where a step is its launches; k = 4: 1.11 x at 4000, 1.02 x at 2048, the same crossover.  Rows that share
 nothing pay 25 to 45 us a step (2 to 3 %) in a pool with slots.
 
+FP8 K/V.  ``model.decode_pool(rows, capacity, kv_dtype="fp8")`` runs on a session whose event-level cache holds OCP e4m3
+codes with one fp32 scale per (row, head, event) for K and one for V -- 136 bytes where the bf16 cache holds 256, per decoded event
+and per row of capacity -- for EVERY row, prompts of their own included.  The admission's store quantizes
+(``mh_kv_store_seqs_rows_fp8``), decode attention dequantizes in registers and attends to the new event's row as the cache holds it
+(``mh_attn_decode_append_rows_fp8``), a fork copies codes and scales bit for bit (``mh_kv_fork_rows_fp8``).  The stated limits:
+  * a request's ids may differ from the same request in a bf16-cache pool (the quantization moves the hidden state by about what the
+    reference's own fp8 restatement says: DESIGN 7.11);
+  * the seeded pool's promise holds as it stands: quantization is per (row, head, event), a row's keys do not depend on its row
+    number, its neighbours or what the row held before, and the new row is attended to quantized -- so a child on its parent's seed
+    repeats the parent and a held-then-forked request equals an uninterrupted one, at equal launch shapes and nothing wider;
+  * a bf16 model and at most 256 rows (``ValueError`` at construction otherwise); not available with prefix slots, nor with
+    ``generate``, ``generate_ragged`` or ``share_prompt``; the token-level cache is what it was.
+A pool made without ``kv_dtype`` takes the session, the graphs and the launches it took.  Measured (one MI355X,
+``profiles/pool_kvq_ab.txt``; ``tools/bench_pool_kvq.py``, tv2o-medium bf16, 64 rows all behind P events, median decode step, fp8
+against bf16): P = 4000: 2.43 against 3.34 ms (1.37 x), 2048: 1.95 against 2.36 (1.21 x), 512: 1.51 against 1.56 (1.03 x), 64: 1.34
+against 1.31 -- fp8 is SLOWER below a few hundred cached events (between the measured 64 and 512), where a step is its launches and
+the kernel converts twice the elements per byte; the attention launch alone gains 1.78 x at 4000 events, under the 1.88 x byte ratio.
+The admitting step is within 0.15 ms either way.  64 rows x 4096 events: 6.85 GB of cache against 12.88 GB.
+
 Out of scope:
   * a background thread or server loop -- the caller owns the loop (and the thread: one pool, one thread);
   * shrinking the row caches of a pool with prefix slots, or a prompt shared ACROSS pools;
@@ -130,12 +149,21 @@ class _Request:
 
 
 class DecodePool:
-    """see the module docstring; made by ``MIDIModel.decode_pool(rows, capacity, generator, seeded, prefix_slots, prefix_capacity)``"""
+    """see the module docstring; made by ``MIDIModel.decode_pool(rows, capacity, generator, seeded, prefix_slots, prefix_capacity,
+    kv_dtype)``"""
 
     def __init__(self, model, rows: int, capacity: int, generator=None, seeded: bool = False, prefix_slots: int = 0,
-                 prefix_capacity: int = 0):
+                 prefix_capacity: int = 0, kv_dtype: Optional[str] = None):
         if int(rows) != rows or rows < 1 or int(capacity) != capacity or capacity < 2:
             raise ValueError(f"decode_pool: {rows} rows of capacity {capacity}")
+        if kv_dtype is not None:
+            if kv_dtype != "fp8":
+                raise ValueError(f"decode_pool: kv_dtype={kv_dtype!r} -- None (the cache in the model's dtype) or \"fp8\"")
+            if prefix_slots or prefix_capacity:
+                raise ValueError("decode_pool: kv_dtype=\"fp8\" is not available together with prefix slots")
+            if rows > 256 or model.dtype != torch.bfloat16:
+                raise ValueError(f"decode_pool: kv_dtype=\"fp8\" needs a bf16 model and at most 256 rows: {model.dtype}, {rows} rows")
+        self.kv_dtype = kv_dtype
         if (prefix_slots or prefix_capacity) and not (
                 all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in (prefix_slots, prefix_capacity))
                 and prefix_slots >= 1 and prefix_capacity >= 1):
@@ -332,6 +360,8 @@ class DecodePool:
         if self.ses is None:
             # (1.0, 0.98, 1 fill a NEW session's buffers through its warm-up pass; every admission overwrites its rows')
             slots = dict(prefix_slots=self.prefix_slots, prefix_capacity=self.prefix_capacity) if self.prefix_slots else {}
+            if self.kv_dtype is not None:
+                slots = dict(kv_dtype=self.kv_dtype)
             ses = self.model._checkout_session(self.rows, self.capacity, 1.0, 0.98, 1, ragged=True, row_params=True,
                                                 seeded=self.seeded, **slots)
             ses.reset()                      # every row free: pos = pos_limit = 0
