@@ -599,6 +599,28 @@ int mh_sample_top_p_k_seeded(const void* logits, int64_t ldl, const uint8_t* fir
  * at token position `pos` (uint32 / float [B, 64], device), through the device function the sampler calls.  A host caller gets a
  * request's variates from it; the tests read the generator through it.                                                         */
 int mh_sample_noise_seeded(const uint64_t* seed, const int32_t* ctr, int pos, int64_t B, uint32_t* bits, float* q, void* stream);
+/* The LOGP forms of the per-row and the seeded sampler (a decode pool with logprobs=True): the argument list of the plain form plus
+ * `logp` (float, DEVICE, required) and `logp_stride` (>= 1).  Row b writes
+ *     logp[b * logp_stride] = z_c - log sum_{v < V} exp(z_v)        fp32, over the row's logits as stored (bf16 or fp32)
+ * for the id c it drew, and nothing else of that buffer -- as out / out_stride, so token step i can be handed logp_rows[:, i].  It is
+ * the MODEL's log-probability: temperature, top-p, top-k, the two masks, the seed and the row have no part in it, and the padding
+ * columns V..ldl-1 never enter.  The sum runs in fp32 with the accurate expf / logf beside the sampler's own statistics pass; its
+ * error bound is derived in tests/ref_logp.py.  A row without any candidate (id 0x7fffffff) writes -inf.  out, out_b, out_c and the
+ * fill_rest entries are the plain form's bit for bit.  Same argument checks under these names; a NULL logp or logp_stride < 1 is
+ * refused by name (MH_ERR_ARG) before any launch.                                                                                */
+int mh_sample_top_p_k_rows_logp(const void* logits, int64_t ldl, const uint8_t* first_mask, int64_t first_stride,
+                                const uint8_t* ban_mask, int64_t ban_stride, int first_lo, int first_hi,
+                                const int32_t* lo_tab, const int32_t* hi_tab, int tab_stride, int max_range, const int64_t* ev,
+                                int pos, const float* q, int64_t* out, int64_t out_stride, int64_t* out_b, int64_t* out_c,
+                                int64_t B, int V, const float* temp, const float* top_p, const int32_t* top_k, int fill_rest,
+                                int64_t fill_id, int dtype, void* stream, float* logp, int64_t logp_stride);
+int mh_sample_top_p_k_seeded_logp(const void* logits, int64_t ldl, const uint8_t* first_mask, int64_t first_stride,
+                                  const uint8_t* ban_mask, int64_t ban_stride, int first_lo, int first_hi,
+                                  const int32_t* lo_tab, const int32_t* hi_tab, int tab_stride, int max_range, const int64_t* ev,
+                                  int pos, const uint64_t* seed, const int32_t* ctr, int64_t* out, int64_t out_stride,
+                                  int64_t* out_b, int64_t* out_c, int64_t B, int V, const float* temp, const float* top_p,
+                                  const int32_t* top_k, int fill_rest, int64_t fill_id, int dtype, void* stream, float* logp,
+                                  int64_t logp_stride);
 
 /* ---- the data-parallel gradient exchange on RCCL (reference: DDP under Lightning, train.py:461-474) -----------------
  * One communicator per process/GPU.  librccl is opened on the first call (dlopen; not a link-time dependency).

@@ -613,7 +613,24 @@ struct SampleArg<true> {
   using I = const int32_t* __restrict__;
 };
 
-template <typename T, int TMAX, bool ROWS = false, bool SEEDED = false>  // TMAX: candidates per lane (64 * TMAX >= the longest mask range of this position)
+//
+// LOGP (mh_sample_top_p_k_rows_logp / mh_sample_top_p_k_seeded_logp; a decode pool with logprobs=True): ROWS or ROWS + SEEDED, plus ONE
+// output -- logp[b * logp_stride] = z_c - log sum_{v < V} exp(z_v) over the RAW logits of the row, c the id the block chose: the
+// model's own log-probability, whatever temperature, top-p, top-k and the masks are.  The statistics pass has every logit of the row
+// in registers: a second (max, sum) pair over to_f(z) runs beside the pair over rnd<T>(z / temp), BEHIND it in every batch, through the
+// same wave and block reductions (LDS partials of its own), with the accurate expf / logf (the bound of tests/ref_logp.py counts 1 ulp
+// each; the plain pair keeps its intrinsics).  z_c is ONE reload of row[id] by lane 0 once the id is known -- an L2 hit on a line the
+// block has just read; the block maximum, the four rescaled partials and the log run under that load.  The output travels as a
+// trailing parameter PACK that only LOGP instantiations fill, so every other instantiation keeps its parameter list, its kernarg
+// layout and its code (DESIGN 7.12 has the per-symbol disassembly comparison).  The sampled id, out_b, out_c and the fill_rest writes
+// are the plain form's: nothing the draw reads is touched.
+struct LogpOut {
+  float* __restrict__ p;  // row b writes p[b * stride] and nothing else
+  int64_t stride;
+};
+__device__ inline LogpOut logp_out(LogpOut o) { return o; }
+
+template <typename T, int TMAX, bool ROWS = false, bool SEEDED = false, bool LOGP = false, typename... LP>  // TMAX: candidates per lane (64 * TMAX >= the longest mask range of this position)
 __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict__ logits, int64_t ldl,
                                                              const uint8_t* __restrict__ first_mask,
                                                              const uint8_t* __restrict__ ban_mask,
@@ -627,7 +644,8 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
                                                              typename SampleArg<ROWS>::F top_p_arg,
                                                              typename SampleArg<ROWS>::I top_k_arg, int fill_rest,
                                                              int64_t fill_id, int64_t first_stride = 0,
-                                                             int64_t ban_stride = 0) {
+                                                             int64_t ban_stride = 0, LP... lp) {
+  static_assert(LOGP ? (ROWS && sizeof...(LP) == 1) : sizeof...(LP) == 0, "the log-probability output belongs to the LOGP forms alone");
   __shared__ float sel_v[SAMPLE_MAX_K];
   __shared__ int sel_i[SAMPLE_MAX_K];
   __shared__ float part_m[4], part_s[4];
@@ -719,6 +737,14 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
   }
   // ---- softmax statistics over the whole vocabulary (logits / temp in the activation dtype, as the reference)
   float m = -INFINITY, ssum = 0.f;
+  [[maybe_unused]] float m2 = -INFINITY, s2 = 0.f;  // (LOGP) the same pair over the raw logits
+  [[maybe_unused]] float* part2 = nullptr;          // (LOGP) its wave partials: max [4], sum [4]
+  // (declared inside the discarded branch, not as part_raw[LOGP ? 8 : 1] beside part_m: the other instantiations then hold no LDS
+  //  object for it at all and keep their group-segment size; a __shared__ array has static storage, so the pointer outlives the block)
+  if constexpr (LOGP) {
+    __shared__ float part_raw[8];
+    part2 = part_raw;
+  }
   constexpr int NZ = 14;  // 14 x 256 = 3584 >= vocab 3406: one batch
   for (int base = 0; base < V; base += NZ * 256) {
     T zr[NZ];
@@ -744,6 +770,25 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
 #pragma unroll
       for (int i = 0; i < NZ; ++i) ssum += __expf(zl[i] - m);
     }
+    if constexpr (LOGP) {  // the raw values of the same registers, in the same order (tests/ref_logp.py, kernel_order)
+      float zw[NZ];
+#pragma unroll
+      for (int i = 0; i < NZ; ++i) {
+        const int c = base + threadIdx.x + 256 * i;
+        zw[i] = c < V ? to_f(zr[i]) : -INFINITY;
+      }
+      float c2 = zw[0];
+#pragma unroll
+      for (int i = 1; i < NZ; ++i) c2 = fmaxf(c2, zw[i]);
+      if (c2 > m2) {
+        s2 *= expf(m2 - c2);  // (m2 = -inf: 0)
+        m2 = c2;
+      }
+      if (m2 > -INFINITY) {
+#pragma unroll
+        for (int i = 0; i < NZ; ++i) s2 += expf(zw[i] - m2);
+      }
+    }
   }
   {
     const float wm = wave_max(m);
@@ -751,6 +796,14 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
     if (lane == 0) {
       part_m[wave] = wm;
       part_s[wave] = ws;
+    }
+  }
+  if constexpr (LOGP) {
+    const float wm2 = wave_max(m2);
+    const float ws2 = wave_sum(m2 > -INFINITY ? s2 * expf(m2 - wm2) : 0.f);
+    if (lane == 0) {
+      part2[wave] = wm2;
+      part2[4 + wave] = ws2;
     }
   }
   if (wave == 0 && lane < SAMPLE_MAX_K) {  // fewer than top_k candidates: the tail has probability 0
@@ -897,6 +950,18 @@ __global__ __launch_bounds__(256) void sample_top_p_k_kernel(const T* __restrict
     if (out_b != nullptr) out_b[b] = id;
     if (out_c != nullptr) out_c[b] = id;
   }
+  if constexpr (LOGP) {
+    if (lane == 0) {
+      const LogpOut lg = logp_out(lp...);
+      const bool drawn = id >= 0 && id < V;  // (no candidate at all: the id is 0x7fffffff, and the value -inf)
+      const float zid = to_f(row[drawn ? id : 0]);  // requested first; the reduction below runs under it
+      const float mx2 = fmaxf(fmaxf(part2[0], part2[1]), fmaxf(part2[2], part2[3]));
+      float tot2 = 0.f;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) tot2 += part2[4 + w] * expf(part2[w] - mx2);
+      lg.p[b * lg.stride] = drawn ? (zid - mx2) - logf(tot2) : -INFINITY;
+    }
+  }
 }
 
 extern "C" int mh_sample_top_p_k(const void* logits, int64_t ldl, const uint8_t* first_mask, const uint8_t* ban_mask,
@@ -995,6 +1060,72 @@ extern "C" int mh_sample_top_p_k_seeded(const void* logits, int64_t ldl, const u
   MH_LAUNCH_CHECK();
   return MH_OK;
 }
+
+// The LOGP forms: the per-row and the seeded form with one more output, logp[b * logp_stride] = the model's log-probability of the id
+// row b drew (fp32).  The argument list of the plain form + (logp, logp_stride); its checks first, under this form's name.
+#define MH_SAMPLE_LOGP_CHECKS(NAME)                                                                                                  \
+  MH_REQUIRE(B > 0 && V > 0 && pos >= 0 && pos < tab_stride && fill_rest >= 0 && fill_rest < out_stride, NAME ": bad args");         \
+  MH_REQUIRE(temp != nullptr && top_p != nullptr && top_k != nullptr,                                                                \
+             NAME ": temp, top_p (float [B]) and top_k (int32 [B]) are device arrays and required");                                 \
+  MH_REQUIRE(first_mask != nullptr && ban_mask != nullptr,                                                                           \
+             NAME ": first_mask and ban_mask (V bytes per row; all zero = nothing banned) are required");                            \
+  MH_REQUIRE(first_stride >= 0 && ban_stride >= 0, NAME ": negative mask stride");                                                   \
+  MH_REQUIRE(pos == 0 || (ev != nullptr && lo_tab != nullptr && hi_tab != nullptr),                                                  \
+             NAME ": position %d needs the event ids and range tables", pos);                                                        \
+  MH_REQUIRE(first_lo >= 0 && first_hi <= V && first_hi - first_lo <= SAMPLE_MAX_RANGE && max_range <= SAMPLE_MAX_RANGE,             \
+             NAME ": a grammar mask spans more than %d ids (first %d..%d, parameters %d)", SAMPLE_MAX_RANGE, first_lo, first_hi,     \
+             max_range);                                                                                                             \
+  MH_REQUIRE(logp != nullptr, NAME ": logp (float, device; row b writes logp[b * logp_stride]) is required");                        \
+  MH_REQUIRE(logp_stride >= 1, NAME ": logp_stride=%lld, at least 1 is needed", (long long)logp_stride)
+
+extern "C" int mh_sample_top_p_k_rows_logp(const void* logits, int64_t ldl, const uint8_t* first_mask, int64_t first_stride,
+                                           const uint8_t* ban_mask, int64_t ban_stride, int first_lo, int first_hi,
+                                           const int32_t* lo_tab, const int32_t* hi_tab, int tab_stride, int max_range,
+                                           const int64_t* ev, int pos, const float* q, int64_t* out, int64_t out_stride,
+                                           int64_t* out_b, int64_t* out_c, int64_t B, int V, const float* temp, const float* top_p,
+                                           const int32_t* top_k, int fill_rest, int64_t fill_id, int dtype, void* stream,
+                                           float* logp, int64_t logp_stride) {
+  MH_SAMPLE_LOGP_CHECKS("sample_top_p_k_rows_logp");
+  MH_REQUIRE(q != nullptr, "sample_top_p_k_rows_logp: q is required");
+  const int span = pos == 0 ? first_hi - first_lo : max_range;
+  const LogpOut lg{logp, logp_stride};
+#define MH_SAMPLE_ROWS_LOGP(TMAX_)                                                                                        \
+  DISPATCH_T(dtype, (sample_top_p_k_kernel<T, TMAX_, true, false, true><<<(int)B, 256, 0, (hipStream_t)stream>>>(        \
+                        (const T*)logits, ldl, first_mask, ban_mask, lo_tab, hi_tab, tab_stride, ev, pos, first_lo, first_hi, q, out, \
+                        out_stride, out_b, out_c, B, V, temp, top_p, top_k, fill_rest, fill_id, first_stride, ban_stride, lg)))
+  if (span <= 128) MH_SAMPLE_ROWS_LOGP(2);
+  else if (span <= 512) MH_SAMPLE_ROWS_LOGP(8);
+  else MH_SAMPLE_ROWS_LOGP(32);
+#undef MH_SAMPLE_ROWS_LOGP
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+extern "C" int mh_sample_top_p_k_seeded_logp(const void* logits, int64_t ldl, const uint8_t* first_mask, int64_t first_stride,
+                                             const uint8_t* ban_mask, int64_t ban_stride, int first_lo, int first_hi,
+                                             const int32_t* lo_tab, const int32_t* hi_tab, int tab_stride, int max_range,
+                                             const int64_t* ev, int pos, const uint64_t* seed, const int32_t* ctr, int64_t* out,
+                                             int64_t out_stride, int64_t* out_b, int64_t* out_c, int64_t B, int V,
+                                             const float* temp, const float* top_p, const int32_t* top_k, int fill_rest,
+                                             int64_t fill_id, int dtype, void* stream, float* logp, int64_t logp_stride) {
+  MH_SAMPLE_LOGP_CHECKS("sample_top_p_k_seeded_logp");
+  MH_REQUIRE(seed != nullptr, "sample_top_p_k_seeded_logp: seed (uint64 [B], device) is required");
+  MH_REQUIRE(ctr != nullptr, "sample_top_p_k_seeded_logp: ctr (int32 [B], device) is required");
+  const int span = pos == 0 ? first_hi - first_lo : max_range;
+  const SeededNoise noise{seed, ctr};
+  const LogpOut lg{logp, logp_stride};
+#define MH_SAMPLE_SEEDED_LOGP(TMAX_)                                                                                      \
+  DISPATCH_T(dtype, (sample_top_p_k_kernel<T, TMAX_, true, true, true><<<(int)B, 256, 0, (hipStream_t)stream>>>(         \
+                        (const T*)logits, ldl, first_mask, ban_mask, lo_tab, hi_tab, tab_stride, ev, pos, first_lo, first_hi, noise, out, \
+                        out_stride, out_b, out_c, B, V, temp, top_p, top_k, fill_rest, fill_id, first_stride, ban_stride, lg)))
+  if (span <= 128) MH_SAMPLE_SEEDED_LOGP(2);
+  else if (span <= 512) MH_SAMPLE_SEEDED_LOGP(8);
+  else MH_SAMPLE_SEEDED_LOGP(32);
+#undef MH_SAMPLE_SEEDED_LOGP
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+#undef MH_SAMPLE_LOGP_CHECKS
 
 // The generator of the seeded form alone: word 0 of the Philox block and the variate made of it, for the 64 ranks of every row,
 // through the device function the sampler calls.  One wave per row.

@@ -103,6 +103,15 @@ mh_attn_decode_append_rows_fp8 (the new row is quantized first and attended to a
 held-then-forked request sees the keys an uninterrupted one saw) and ``fork`` copies through mh_kv_fork_rows_fp8.  The graphs are
 captured from the same schedule and nothing is recaptured.  Not with prefix slots or a shared prompt; ``prefill`` and
 ``prefill_ragged`` refuse such a session.  ``kv_dtype=None`` is the session as it was: the same key, buffers and launches.
+
+``logprobs`` (row_params sessions; seeded or not, with or without prefix slots or the fp8 cache; decode_pool(logprobs=True), DESIGN
+7.12): the token steps call the ``_logp`` form of their sampler (mh_sample_top_p_k_rows_logp / mh_sample_top_p_k_seeded_logp) -- the
+same ids bit for bit -- which also writes ``logp_rows[:, i]`` (fp32 [B, T]): the model's own log-probability z_c - log sum exp z of
+the id each row drew at token position i, whatever the row's temperature, top-p, top-k and masks.  ``sample_event`` copies the buffer
+to a pinned host block on the copy stream beside ``seq``, under the same one synchronise, and leaves the event's values in
+``last_logp`` (np.float32 [B, T]; positions past an event's arity hold the pad token's value or, in the step-by-step form, what an
+earlier event left: the caller sums positions 0..arity).  Only the sampler call changes: admissions, forks and releases recapture
+nothing.  The key's form gains ``("logp",)`` at its end; ``logprobs=False`` is the session as it was: the same key, buffers and launches.
 """
 from __future__ import annotations
 
@@ -136,7 +145,7 @@ def graphs_enabled(device: torch.device) -> bool:
 class DecodeSession:
     def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int, shared_capacity: int = 0,
                  ragged: bool = False, row_params: bool = False, seeded: bool = False, prefix_slots: int = 0,
-                 prefix_capacity: int = 0, kv_dtype: Optional[str] = None):
+                 prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False):
         tok = model.tokenizer
         self.model, self.B, self.cap, self.temp = model, B, capacity, float(temp)
         self.top_p, self.top_k = float(top_p), int(top_k)
@@ -146,8 +155,9 @@ class DecodeSession:
         self.seeded = bool(seeded)
         self.prefix_slots, self.prefix_capacity = int(prefix_slots), int(prefix_capacity)
         self.kv_dtype = kv_dtype
+        self.logprobs = bool(logprobs)
         self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params, seeded,
-                                 prefix_slots, prefix_capacity, kv_dtype)
+                                 prefix_slots, prefix_capacity, kv_dtype, logprobs)
         dev, dt = model.device, model.dtype
         self.T, self.V, self.Vp = tok.max_token_seq, tok.vocab_size, model.vocab_padded
         spec, tspec = model._specs["net"], model._specs["net_token"]
@@ -200,6 +210,9 @@ class DecodeSession:
         self.hidden = torch.zeros((B, spec.D), dtype=dt, device=dev)
         self.seq = torch.zeros((B, self.T), dtype=torch.long, device=dev)  # tokens of the event being sampled
         self.samples_in = torch.zeros((B,), dtype=torch.long, device=dev)  # token sampled at the previous position
+        # (logprobs) the model's log-probability of every token of the event being sampled, written by the token steps' samplers
+        self.logp_rows = torch.zeros((B, self.T), dtype=torch.float32, device=dev) if self.logprobs else None
+        self.last_logp = None  # ... and the host copy sample_event() leaves: np.float32 [B, T] of the event it returned
         self.ev = torch.zeros((B,), dtype=torch.long, device=dev)          # event id (token 0) of the current event
         self.pad_id = tok.pad_id
         self.neg1 = torch.full((B,), -1, dtype=torch.int32, device=dev)
@@ -243,7 +256,9 @@ class DecodeSession:
 
     @staticmethod
     def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False, row_params=False, seeded=False,
-                 prefix_slots=0, prefix_capacity=0, kv_dtype=None):
+                 prefix_slots=0, prefix_capacity=0, kv_dtype=None, logprobs=False):
+        if logprobs and not (ragged and row_params):
+            raise ValueError("DecodeSession: logprobs is a form of the per-row session -- it needs ragged=True, row_params=True")
         if kv_dtype is not None:
             if kv_dtype != "fp8":
                 raise ValueError(f"DecodeSession: kv_dtype={kv_dtype!r} -- None (the cache in the model's dtype) or \"fp8\"")
@@ -276,6 +291,8 @@ class DecodeSession:
                 form += (("slots", int(prefix_slots), int(prefix_capacity)),)
             if kv_dtype is not None:  # (likewise: only an fp8 session carries it)
                 form += (("kv", "fp8"),)
+            if logprobs:  # (likewise, at the end: only a session whose samplers write log-probabilities carries it)
+                form += (("logp",),)
             return (model._flat.data_ptr(), model._flat.dtype, B, capacity, form)
         key = (model._flat.data_ptr(), model._flat.dtype, B, capacity, float(temp), float(top_p), int(top_k))
         if ragged:
@@ -351,19 +368,22 @@ class DecodeSession:
             # one launch instead of sample_top_p_k's ~25: the Exp(1) noise torch.multinomial would draw internally
             # (empty_like(probs).exponential_(1, generator)) is drawn here (eager form) or by the noise graph ahead of the
             # step (draw=False), the rest is mh_sample_top_p_k
+            # (logprobs) the ``_logp`` form of the row's sampler: the same ids, and logp_rows[:, i] = the model's log-probability of
+            # the id each row drew, handed over behind the ban mask; without the option the call is the plain form's as it was
+            lp = (self.logp_rows[:, i],) if self.logprobs else ()
+            tail = dict(out_b=self.samples_in, out_c=self.ev if i == 0 else None, first_span=self.first_span,
+                        max_range=self.max_range[i], fill_rest=self.T - 1 if i == 0 else 0, fill_id=self.pad_id)
             if self.seeded:  # nothing is drawn: row b's variates follow from seed_rows[b] and pos[b], the index of this event
-                ops.sample_top_p_k_seeded(self.logits, self.first_mask, self.lo_tab, self.hi_tab, self.ev, i, self.seed_rows, self.pos,
-                                          self.seq[:, i], self.V, self.temp_rows, self.top_p_rows, self.top_k_rows, self.ban,
-                                          out_b=self.samples_in, out_c=self.ev if i == 0 else None, first_span=self.first_span,
-                                          max_range=self.max_range[i], fill_rest=self.T - 1 if i == 0 else 0, fill_id=self.pad_id)
+                op = ops.sample_top_p_k_seeded_logp if self.logprobs else ops.sample_top_p_k_seeded
+                op(self.logits, self.first_mask, self.lo_tab, self.hi_tab, self.ev, i, self.seed_rows, self.pos, self.seq[:, i], self.V,
+                   self.temp_rows, self.top_p_rows, self.top_k_rows, self.ban, *lp, **tail)
                 return
             if draw:
                 self.q_all[i].exponential_(1.0, generator=generator)
             if self.row_params:  # the same kernel, row b on temp_rows[b], top_p_rows[b], top_k_rows[b] and its own two masks
-                ops.sample_top_p_k_rows(self.logits, self.first_mask, self.lo_tab, self.hi_tab, self.ev, i, self.q_all[i],
-                                        self.seq[:, i], self.V, self.temp_rows, self.top_p_rows, self.top_k_rows, self.ban,
-                                        out_b=self.samples_in, out_c=self.ev if i == 0 else None, first_span=self.first_span,
-                                        max_range=self.max_range[i], fill_rest=self.T - 1 if i == 0 else 0, fill_id=self.pad_id)
+                op = ops.sample_top_p_k_rows_logp if self.logprobs else ops.sample_top_p_k_rows
+                op(self.logits, self.first_mask, self.lo_tab, self.hi_tab, self.ev, i, self.q_all[i], self.seq[:, i], self.V,
+                   self.temp_rows, self.top_p_rows, self.top_k_rows, self.ban, *lp, **tail)
                 return
             ops.sample_top_p_k(self.logits, self.first_mask, self.lo_tab, self.hi_tab, self.ev, i, self.q_all[i], self.seq[:, i],
                                self.V, self.temp, self.top_p, self.top_k, out_b=self.samples_in,
@@ -411,6 +431,7 @@ class DecodeSession:
             self.copy_stream = torch.cuda.Stream()
             self.steps_done = torch.cuda.Event()
             self.seq_host = torch.empty((self.B, self.T), dtype=torch.long).pin_memory()
+            self._pin_logp()
         elif self.fused_sampler:
             # the event's draws in one graph (the only one that touches the generator) ...
             self.g_noise = torch.cuda.CUDAGraph()
@@ -433,10 +454,15 @@ class DecodeSession:
             self.copy_stream = torch.cuda.Stream()
             self.steps_done = torch.cuda.Event()
             self.seq_host = torch.empty((self.B, self.T), dtype=torch.long).pin_memory()
+            self._pin_logp()
         else:
             for i in range(self.T):
                 self._capture_step(i)
         self.reset()
+
+    def _pin_logp(self) -> None:
+        """(logprobs) the pinned host block logp_rows is copied to beside seq, under the event's one synchronise"""
+        self.logp_host = torch.empty((self.B, self.T), dtype=torch.float32).pin_memory() if self.logprobs else None
 
     def _capture_step(self, i: int):
         """a graph of token step i alone (the step-by-step form; with the fused sampler only tests / debugging use it: the
@@ -1000,13 +1026,21 @@ class DecodeSession:
                 with torch.cuda.stream(self.copy_stream):
                     if _COPY_PAGEABLE:  # (A/B: a blocking pageable copy on the copy stream instead of pinned + stream sync)
                         event = self.seq.cpu().numpy().copy()
+                        if self.logprobs:
+                            self.last_logp = self.logp_rows.cpu().numpy().copy()
                     else:
                         self.seq_host.copy_(self.seq, non_blocking=True)
+                        if self.logprobs:  # beside seq on the copy stream: the same one synchronise covers both
+                            self.logp_host.copy_(self.logp_rows, non_blocking=True)
                 if not _COPY_PAGEABLE:
                     self.copy_stream.synchronize()  # the one host sync per event
                     event = self.seq_host.numpy().copy()
+                    if self.logprobs:
+                        self.last_logp = self.logp_host.numpy().copy()
             else:
                 event = self.seq.cpu().numpy().copy()  # the one host sync per event
+                if self.logprobs:
+                    self.last_logp = self.logp_rows.cpu().numpy().copy()
             n, end_all = self.n_steps_of(self._live_ids(event[:, 0].tolist(), live))
             self.consumed(n)
             return event, end_all
@@ -1016,4 +1050,6 @@ class DecodeSession:
             if i == 0:
                 n_steps, end_all = self.n_steps_of(self._live_ids(self.ev.tolist(), live))  # (a host sync)
             i += 1
+        if self.logprobs:  # (step-by-step form: positions the break rule skipped keep what an earlier event left there)
+            self.last_logp = self.logp_rows.cpu().numpy().copy()
         return self.seq.cpu().numpy().copy(), end_all  # (a CPU tensor would share memory with the session buffer)

@@ -422,6 +422,57 @@ class MIDIModel(nn.Module):
         out.append(st.norm.weight)
         return out
 
+    SCORE_CHUNK_ROWS = 32768  # token rows per lm_head + cross-entropy chunk of score() (the training loss head's default)
+
+    @torch.no_grad()
+    def score(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
+        """(ours) x (B, S, 8) int64 -> fp32 (B, S - 1) on the device: entry [b, t] is the model's log-likelihood of event t + 1 given
+        events <= t -- ll(e) = sum over the event's token positions 0..arity of (z_c - log sum exp z), pad targets ignored: exactly
+        the quantity the training loss sums (hidden = forward(x[:, :-1]), the token stack teacher-forced on x[:, 1:]), so
+        ``-score(x).sum() / (number of non-pad targets)`` is ``validation_step``'s loss on x.  ``lengths`` (B ints, optional): row b
+        holds lengths[b] events; events at index >= lengths[b], and events made of pad only, give exactly 0.  The same quantity
+        ``DecodePool.logprobs`` reports for generated events.  Runs on the existing kernels -- mh_cross_entropy
+        returns the per-token loss -- chunked over rows as the training loss head is; nothing is kept for a backward."""
+        self._require_gpu()
+        if x.dim() != 3 or x.shape[1] < 2:
+            raise ValueError(f"score: expected (batch, events >= 2, tokens) ids, got shape {tuple(x.shape)}")
+        B, S1, T = x.shape
+        if lengths is not None:
+            lengths = [int(n) for n in lengths]
+            if len(lengths) != B or any(not 0 <= n <= S1 for n in lengths):
+                raise ValueError(f"score: lengths {lengths} for a batch of {B} rows of {S1} events")
+        tok = self.tokenizer
+        hidden = self.forward(x[:, :-1])  # (checks the ids; forward-only schedule under no_grad)
+        dev, dty = self.device, self.dtype
+        y = x[:, 1:].to(device=dev, dtype=torch.long).contiguous()
+        S = S1 - 1
+        tspec, Wt = self._specs["net_token"], self._W["net_token"]
+        D, V, Vp = tspec.D, tok.vocab_size, self.vocab_padded
+        N = B * S
+        R = N * T
+        y_t = y.view(N, T)
+        seq = torch.empty((N, T, D), dtype=dty, device=dev)
+        ops.concat_tok_fwd(hidden.reshape(N, D), y_t, Wt.embed, seq, T)
+        h, _ = engine.stack_forward(tspec, Wt, seq.view(R, D), N, T, self.rope("net_token"), save=False,
+                                    folded=self._folded_for(tspec, seq.view(R, D)))
+        del seq
+        targets = y_t.reshape(R)
+        row_loss = torch.empty(R, dtype=torch.float32, device=dev)
+        lm_w = self.lm_head.weight.data
+        chunk = max(T, (self.SCORE_CHUNK_ROWS // T) * T)
+        logits = torch.empty((min(chunk, R), Vp), dtype=dty, device=dev)
+        for r0 in range(0, R, chunk):
+            r1 = min(R, r0 + chunk)
+            lg = logits[: r1 - r0]
+            ops.gemm_nt(h[r0:r1], lm_w, lg[:, :V])
+            ops.cross_entropy(lg, V, targets[r0:r1], row_loss[r0:r1], None, None, None, tok.pad_id)
+        # (a pad target's row_loss is 0: ignore_index; the sum over an event's 8 rows is its ll, negated)
+        out = -row_loss.view(B, S, T).sum(-1)
+        if lengths is not None:  # event t + 1 exists iff t + 1 < lengths[b]
+            keep = torch.arange(1, S1, device=dev)[None, :] < torch.tensor(lengths, device=dev)[:, None]
+            out = torch.where(keep, out, torch.zeros_like(out))
+        return out
+
     def sample_top_p_k(self, probs, p, k, generator=None):
         """midi_model.py:152-165, op for op (torch.sort / cumsum / multinomial), so a seeded
         ``torch.Generator`` is consumed exactly as the reference consumes it."""
@@ -815,7 +866,7 @@ class MIDIModel(nn.Module):
         return self._ragged_prompts([prompt], rp["max_len"], crop)[0], rp
 
     def decode_pool(self, rows: int, capacity: int, generator=None, seeded: bool = False, prefix_slots: int = 0,
-                    prefix_capacity: int = 0, kv_dtype: Optional[str] = None):
+                    prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False):
         """(ours) a ``pool.DecodePool`` on this model: ``rows`` decode rows that requests are admitted into and released from
         while the batch runs (continuous batching).  ``capacity``: cache rows per decode row; a request needs
         max_len + 1 <= capacity (the session's own capacity is rounded up as every session's is, 256 x 2^k).  The pool takes one
@@ -826,9 +877,13 @@ class MIDIModel(nn.Module):
         events, and ``submit(..., share_prefix=True)`` stores a prompt of at most Pmax events in one, read ONCE per decoded event
         for all the rows that continue it -- siblings (``n=k``) and fork children (pool.py).
         ``kv_dtype="fp8"``: the rows' event-level K/V is cached as e4m3 codes with a scale per head and event, 0.53 x the bytes
-        (pool.py "FP8 K/V"); a bf16 model, at most 256 rows, not with prefix slots (``ValueError``).  Nothing is
-        launched here."""
+        (pool.py "FP8 K/V"); a bf16 model, at most 256 rows, not with prefix slots (``ValueError``).
+        ``logprobs=True``: ``pool.logprobs(rid)`` gives the model's log-likelihood of every event a request generated (pool.py
+        "LOG-LIKELIHOODS"); with any of the options above.  Nothing is launched here."""
         from .pool import DecodePool
+        if logprobs:
+            return DecodePool(self, rows, capacity, generator, seeded, prefix_slots, prefix_capacity, kv_dtype=kv_dtype,
+                              logprobs=True)
         if kv_dtype is not None:
             return DecodePool(self, rows, capacity, generator, seeded, prefix_slots, prefix_capacity, kv_dtype=kv_dtype)
         if prefix_slots or prefix_capacity:
@@ -836,13 +891,15 @@ class MIDIModel(nn.Module):
         return DecodePool(self, rows, capacity, generator, seeded)
 
     def generate_pool(self, requests, rows: int, capacity: Optional[int] = None, generator=None,
-                      kv_dtype: Optional[str] = None) -> list:
+                      kv_dtype: Optional[str] = None, logprobs: bool = False) -> list:
         """(ours) ``requests``: a list of dicts, each the keyword arguments of ``DecodePool.submit`` (``prompt`` and any of max_len,
         temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change, disable_channels, seed).  If EVERY request
         carries ``"seed"`` the pool is a seeded one; some with and some without is a ``ValueError``.  They are submitted in order
         to one pool of ``rows`` rows and stepped until all are done: a request waits only until a row is free, and a row that
         finishes is handed to the next request at once.  -> a list of ``np.ndarray (<= max_len, 8) int64``, request i's at index
-        i, its prompt in front.  ``capacity`` defaults to the largest max_len + 1.  ``kv_dtype``: as ``decode_pool`` takes it."""
+        i, its prompt in front.  ``capacity`` defaults to the largest max_len + 1.  ``kv_dtype``: as ``decode_pool`` takes it.
+        ``logprobs=True``: -> a list of ``(events, logprobs)`` pairs instead, ``logprobs`` the request's ``DecodePool.logprobs``
+        array (np.float32, one value per generated event, aligned with ``events[len(prompt):]``)."""
         requests = list(requests)
         if not requests:
             return []
@@ -852,10 +909,14 @@ class MIDIModel(nn.Module):
         if with_seed not in (0, len(requests)):
             raise ValueError(f"generate_pool: {with_seed} of {len(requests)} requests carry a seed -- all of them or none")
         kvq = dict(kv_dtype=kv_dtype) if kv_dtype is not None else {}
+        if logprobs:
+            kvq["logprobs"] = True
         with self.decode_pool(rows, capacity, generator, seeded=with_seed > 0, **kvq) as pool:
             ids = [pool.submit(**r) for r in requests]
             while pool.pending():
                 pool.step()
+            if logprobs:
+                return [(pool.result(i), pool.logprobs(i)) for i in ids]
             return [pool.result(i) for i in ids]
 
     def _generate_events(self, inp, batch_size, max_len, temp, top_p, top_k, generator, ban_eos, disable_patch_change,
@@ -903,8 +964,10 @@ class MIDIModel(nn.Module):
     # decode sessions: buffers + captured graphs, one per concurrent generate() call (decode.py)
     def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int, shared_need: int = 0,
                           ragged: bool = False, row_params: bool = False, seeded: bool = False, prefix_slots: int = 0,
-                          prefix_capacity: int = 0, kv_dtype: Optional[str] = None):
-        """``kv_dtype`` = "fp8" (row_params only): the session whose event-level cache holds e4m3 codes and scales (DecodeSession); a
+                          prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False):
+        """``logprobs`` (row_params only): the session whose samplers also write the drawn ids' log-probabilities (DecodeSession); a
+        pooled session of its own kind, False: the session as it was.
+        ``kv_dtype`` = "fp8" (row_params only): the session whose event-level cache holds e4m3 codes and scales (DecodeSession); a
         pooled session of its own kind, None: the session as it was.
         ``prefix_slots`` / ``prefix_capacity`` (row_params only): a session with that many prefix slots of that many rows
         (DecodeSession; the capacity is rounded up by the doubling rule too); 0: the session as it was.
@@ -928,7 +991,10 @@ class MIDIModel(nn.Module):
             pcap = 256
             while pcap < prefix_capacity:
                 pcap *= 2
-        if kv_dtype is not None:
+        if logprobs:
+            key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap,
+                                         kv_dtype, True)
+        elif kv_dtype is not None:
             key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap,
                                          kv_dtype)
         elif prefix_slots:
@@ -947,6 +1013,9 @@ class MIDIModel(nn.Module):
         if found is not None:
             found.refresh()  # weights may have been trained / merged since the session derived its folded copies
             return found
+        if logprobs:
+            return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap, kv_dtype,
+                                 logprobs=True)
         if kv_dtype is not None:
             return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap, kv_dtype)
         if prefix_slots:

@@ -619,9 +619,14 @@ _FORK = ("kv_fork_rows",)
 _SHARE = ("attn_prefix_partial_slots", "attn_decode_append_rows_shared")
 # ... and the store, decode attention and fork over the 8-bit K/V cache (ops_kvq.py; stand-ins in tests/emu_kvq.py)
 _KVQ = ("kv_store_seqs_rows_fp8", "attn_decode_append_rows_fp8", "kv_fork_rows_fp8")
+# ... and the per-row and seeded samplers that also write the drawn id's log-probability (ops_logp.py; stand-ins in tests/emu_logp.py)
+_LOGP = ("sample_top_p_k_rows_logp", "sample_top_p_k_seeded_logp")
 
 
 def __getattr__(name: str):
+    if name in _LOGP:
+        from . import ops_logp
+        return getattr(ops_logp, name)
     if name in _KVQ:
         from . import ops_kvq
         return getattr(ops_kvq, name)

@@ -104,6 +104,25 @@ against 1.31 -- fp8 is SLOWER below a few hundred cached events (between the mea
 the kernel converts twice the elements per byte; the attention launch alone gains 1.78 x at 4000 events, under the 1.88 x byte ratio.
 The admitting step is within 0.15 ms either way.  64 rows x 4096 events: 6.85 GB of cache against 12.88 GB.
 
+LOG-LIKELIHOODS.  ``model.decode_pool(rows, capacity, logprobs=True)`` -- with any of the options above -- runs on a
+session whose token steps call the ``_logp`` form of their sampler (``mh_sample_top_p_k_rows_logp`` /
+``mh_sample_top_p_k_seeded_logp``): the same ids bit for bit, plus the MODEL's log-probability ``z_c - log sum_v exp(z_v)`` of every
+token drawn, over the raw logits -- independent of temperature, top-p, top-k, the masks, the seed and the row, so values of requests
+with different settings compare, and it is what the training loss sums.  ``pool.logprobs(rid)`` -> ``np.float32 [len(result(rid)) -
+len(prompt)]``: ``ll`` of every event the request generated, aligned with ``result(rid)[len(prompt):]``; an event's ``ll`` is the sum
+over its token positions 0..arity (the host sums them in fp32 with the grammar's arity table; EOS counts position 0 alone, the pad
+positions behind an event's parameters count nothing).  A fork child's array covers its own events -- the inherited ones are its
+prompt; a held request keeps its array; a row handed to a later request starts empty.  ``step()`` and ``result()`` are unchanged, and
+``MIDIModel.score(x)`` gives the same quantity for given sequences.  The stated limits:
+  * the values are exact on the logits the decode path produced (fp32 sums, error bound derived in tests/ref_logp.py); what bf16
+    activations do to the logits themselves is the decode path's, as for the ids;
+  * the seeded pool's promise extends as it stands: a request's log-likelihoods are a function of what its ids are a function of;
+  * not the probability under the filtered (temperature / top-p / top-k / masked) distribution, and no top-n alternatives;
+  * ``generate``, ``generate_ragged`` and ``share_prompt`` report none; ``logprobs()`` on a pool made without the option is a
+    ``ValueError``.
+A pool made without ``logprobs`` takes the session, the graphs and the launches it took.  Measured: DESIGN 7.12
+(``tools/bench_pool_logp.py``, ``profiles/pool_logp_ab.txt``).
+
 Out of scope:
   * a background thread or server loop -- the caller owns the loop (and the thread: one pool, one thread);
   * shrinking the row caches of a pool with prefix slots, or a prompt shared ACROSS pools;
@@ -138,11 +157,13 @@ class _Request:
     # (rp["seed"]: a seeded pool's request; prompt: a child's holds its parent's result at the fork; group: the size of the sibling
     #  group this request LEADS in the queue, 0 for the siblings behind it; kw: the settings as given, a child's defaults)
     #  share: the request continues a prompt that sits in a prefix slot -- a share_prefix submit, its siblings, their fork children)
-    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done", "hold", "held", "eos", "group", "kw", "share")
+    #  logp: ll of every event the request generated itself, beside ``events`` (a pool with logprobs=True; empty otherwise)
+    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done", "hold", "held", "eos", "group", "kw", "share", "logp")
 
     def __init__(self, prompt: np.ndarray, rp: dict, kw: dict, hold: bool = False, group: int = 1, share: bool = False):
         self.prompt, self.rp, self.max_len, self.kw, self.share = prompt, rp, rp["max_len"][0], kw, bool(share)
         self.events: List[np.ndarray] = []
+        self.logp: List[float] = []
         self.row: Optional[int] = None
         self.done = False
         self.hold, self.held, self.eos, self.group = bool(hold), False, False, group
@@ -150,10 +171,10 @@ class _Request:
 
 class DecodePool:
     """see the module docstring; made by ``MIDIModel.decode_pool(rows, capacity, generator, seeded, prefix_slots, prefix_capacity,
-    kv_dtype)``"""
+    kv_dtype, logprobs)``"""
 
     def __init__(self, model, rows: int, capacity: int, generator=None, seeded: bool = False, prefix_slots: int = 0,
-                 prefix_capacity: int = 0, kv_dtype: Optional[str] = None):
+                 prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False):
         if int(rows) != rows or rows < 1 or int(capacity) != capacity or capacity < 2:
             raise ValueError(f"decode_pool: {rows} rows of capacity {capacity}")
         if kv_dtype is not None:
@@ -164,6 +185,7 @@ class DecodePool:
             if rows > 256 or model.dtype != torch.bfloat16:
                 raise ValueError(f"decode_pool: kv_dtype=\"fp8\" needs a bf16 model and at most 256 rows: {model.dtype}, {rows} rows")
         self.kv_dtype = kv_dtype
+        self.want_logprobs = bool(logprobs)
         if (prefix_slots or prefix_capacity) and not (
                 all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in (prefix_slots, prefix_capacity))
                 and prefix_slots >= 1 and prefix_capacity >= 1):
@@ -330,6 +352,15 @@ class DecodePool:
             del self.requests[rid]
         return out
 
+    def logprobs(self, rid: int) -> np.ndarray:
+        """(a pool made with ``logprobs=True``) request ``rid``'s log-likelihoods so far: ``np.float32 [len(result(rid)) -
+        len(prompt)]``, entry j the model's ll of the j-th event the request generated -- aligned with
+        ``result(rid)[len(prompt):]`` (a fork child's prompt is what it inherited: its array covers its own events).  See the module
+        docstring, "LOG-LIKELIHOODS".  ``ValueError`` on a pool made without the option."""
+        if not self.want_logprobs:
+            raise ValueError("DecodePool.logprobs: this pool keeps no log-likelihoods -- decode_pool(..., logprobs=True)")
+        return np.asarray(self.requests[rid].logp, dtype=np.float32)
+
     def results(self) -> Dict[int, np.ndarray]:
         """{id: result(id)} of every finished request the pool still knows"""
         return {rid: self.result(rid) for rid, r in self.requests.items() if r.done}
@@ -362,6 +393,8 @@ class DecodePool:
             slots = dict(prefix_slots=self.prefix_slots, prefix_capacity=self.prefix_capacity) if self.prefix_slots else {}
             if self.kv_dtype is not None:
                 slots = dict(kv_dtype=self.kv_dtype)
+            if self.want_logprobs:  # (the call without the option is the call it was)
+                slots["logprobs"] = True
             ses = self.model._checkout_session(self.rows, self.capacity, 1.0, 0.98, 1, ragged=True, row_params=True,
                                                 seeded=self.seeded, **slots)
             ses.reset()                      # every row free: pos = pos_limit = 0
@@ -452,12 +485,17 @@ class DecodePool:
             more = any(len(r.prompt) + len(r.events) + 1 < r.max_len or r.hold for r in running)
             speculative = more and ses.g_steps is not None and _SPECULATIVE_NET
             event, _ = ses.sample_event(then_net=speculative, live=live)
+            if self.want_logprobs:  # ll of an event: its token positions 0..arity, summed here in fp32 (one running sum over the
+                #                     block, position by position); EOS is position 0 alone
+                logp, arity = np.cumsum(ses.last_logp, axis=1, dtype=np.float32), self.model._grammar()[3]
             out, finished, keep = [], [], []
             for row, rid in sorted(self.occupied.items(), key=lambda kv: kv[1]):
                 r = self.requests[rid]
                 ev = event[row].copy()
                 r.events.append(ev)
                 r.eos = bool(ev[0] == eos)
+                if self.want_logprobs:
+                    r.logp.append(logp[row, 0 if r.eos else arity[int(ev[0])]])
                 r.done = r.eos or len(r.prompt) + len(r.events) >= r.max_len
                 if r.done:
                     (keep if r.hold and not r.eos else finished).append(row)
