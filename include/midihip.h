@@ -193,6 +193,33 @@ int mh_gemm_skinny(const void* A, int64_t lda, const void* W, int64_t ldw, void*
 int mh_gemm_skinny_wide(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* R,
                         int64_t ldr, int mode, float norm_eps, const int64_t* row_ids, const int64_t* res_ids, int64_t M,
                         int64_t N, int64_t K, int dtype, void* stream);
+/* ---- a LoRA adapter per row of a decode batch, unmerged (1 <= M <= 256 rows, bf16; the tiling follows mh_gemm_skinny up to 64
+ * rows and mh_gemm_skinny_wide beyond, so the main loop of a projection is the code of those entry points, shape for shape).
+ * A row's projection becomes x W^T + s (x A^T) B^T with A, B, s of the row's adapter (peft's LoraLayer, unmerged):
+ *
+ *   mh_lora_shrink_rows  T[m, n] = row_adapter[m] == slot(n) ? bf16(slot_scale[slot(n)] * sum_k A[m,k] W[n,k]) : 0
+ *                        W = the stacked LoRA-A matrices [parts * G * R, K], rows laid out [part][slot][R], slot(n) = (n / R) % G;
+ *                        row_adapter int32 [M] (-1: no adapter), slot_scale fp32 [G] (alpha / r of the adapter a slot holds).
+ *                        EVERY element of T[M, parts * G * R] is written (zeros included).  row_ids as in mh_gemm_skinny.  No
+ *                        norm: the caller folds the RMSNorm weight into W where the consumer normalises, and the consumer's
+ *                        row scale covers T.  R a multiple of 8, K of 256.
+ *   mh_gemm_skinny_ext   mh_gemm_skinny / _wide with a second operand pair: behind the K loop the accumulator of weight row w goes
+ *                        on over T[m, part(w) K2 .. + K2) . Bst[w, 0 .. K2), part(w) = w / (rows(W) / parts), rows(W) = 2N for
+ *                        MH_SKINNY_GATEUP.  norm_eps, R, row_ids / res_ids and the SwiGLU epilogue apply to the sum; the sum of
+ *                        squares behind norm_eps is taken from A alone; T is read at row m (never through row_ids).
+ *                        With Bst[w, g R + j] = B_g[w, j] and T from mh_lora_shrink_rows this is the LoRA expand: a row's T is
+ *                        non-zero only in the block of its slot, a row without adapter adds exact zeros.
+ *                        REFUSED before any launch: K2 not a multiple of 256; a part boundary inside a workgroup's column block
+ *                        (plain: rows(W) / parts must be a multiple of 16, of 32 for N >= 2048; gate|up: parts 1, 2, or
+ *                        rows / parts a multiple of 16 dividing N); operands past 32-bit element offsets (as the entry points
+ *                        above, and rows(W) * ldb, rows * ldt < 2^31); anything but bf16. */
+int mh_lora_shrink_rows(const void* A, int64_t lda, const void* W, int64_t ldw, void* T, int64_t ldt,
+                        const int32_t* row_adapter, const float* slot_scale, const int64_t* row_ids, int64_t M, int64_t K,
+                        int G, int R, int parts, int dtype, void* stream);
+int mh_gemm_skinny_ext(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* R,
+                       int64_t ldr, const void* T, int64_t ldt, const void* Bst, int64_t ldb, int mode, float norm_eps,
+                       const int64_t* row_ids, const int64_t* res_ids, int64_t M, int64_t N, int64_t K, int64_t K2, int parts,
+                       int dtype, void* stream);
 /* out[C,R] = in[R,C]^T (operand re-layout for dgrad/wgrad). */
 int mh_transpose(const void* in, int64_t ldi, void* out, int64_t ldo, int64_t rows, int64_t cols, int dtype,
                  void* stream);

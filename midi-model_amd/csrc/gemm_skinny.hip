@@ -42,12 +42,37 @@ namespace {
 // which put its wait at the top of the kernel.  Now: every argument is touched at entry (one batch of scalar loads), the
 // residual stays raw until the epilogue, and a batch's BCH x (NBT + MB) fragment loads are all requested before a
 // sched_barrier, behind which the MFMAs run.
-template <int MODE, int NBT, int NW, bool RSTD, int MB, int BCH>
+//
+// EXT (the per-request LoRA forms, entry points mh_gemm_skinny_ext / mh_lora_shrink_rows; 0 = the kernel as it was, nothing of
+// `x` is touched):
+//   1  a second operand pair: behind the K loop every wave goes on over K2 more columns, weight row w against
+//      T[m, part(w) K2 .. + K2) and Bst[w, 0 .. K2), into the SAME accumulators -- so the row scale, the residual, the gathers and
+//      the SwiGLU epilogue apply to the sum.  T is indexed by the output row m itself (never through row_ids) and does not enter
+//      the sum of squares.  The host guarantees that a column block lies inside one part (gate|up: each of its two blocks does).
+//   2  the masking epilogue of the LoRA shrink (plain form, no residual, no row scale): column n belongs to slot (n / R) % G;
+//      the stored value is bf16(slot_scale[slot] acc) where row_adapter[m] == slot and +0 elsewhere -- every element is written.
+//      R is a multiple of 8 (host), so the 4 or 8 columns of a writer thread share one slot.
+struct SkinnyExt {
+  const bf16* T;            // EXT 1: [M, >= parts K2]
+  const bf16* Bst;          // EXT 1: [rows(W), >= K2]
+  unsigned ldt, ldb;
+  int K2, rows_per_part;    // EXT 1
+  const int* row_adapter;   // EXT 2: [M], -1 = none
+  const float* slot_scale;  // EXT 2: [G]
+  int G, R;                 // EXT 2
+};
+
+struct SkinnyNoExt {};  // EXT 0: the trailing kernel argument holds nothing
+template <int EXT> struct SkinnyExtArg { typedef SkinnyExt type; };
+template <> struct SkinnyExtArg<0> { typedef SkinnyNoExt type; };
+
+template <int MODE, int NBT, int NW, bool RSTD, int MB, int BCH, int EXT = 0>
 __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16* __restrict__ A, int64_t lda,
                                                           const bf16* __restrict__ W, int64_t ldw, bf16* __restrict__ C,
                                                           int64_t ldc, const bf16* __restrict__ R, int64_t ldr, int M, int N,
                                                           int K, float norm_eps, const int64_t* __restrict__ row_ids,
-                                                          const int64_t* __restrict__ res_ids, int vec_store) {
+                                                          const int64_t* __restrict__ res_ids, int vec_store,
+                                                          const typename SkinnyExtArg<EXT>::type x) {
   constexpr int NB = NBT * 16;
   constexpr int MR = MB * 16;  // rows of this workgroup
   // rows padded to NB + 4 floats: 16-byte aligned, so a lane's four accumulator values go in with one ds_write_b128 and a writer's
@@ -120,6 +145,16 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16* __rest
     for (int j = 0; j < CPT; ++j) rraw[j] = rsrc[j];
   }
 
+  // EXT 2: the writer's adapter and its column group's slot scale, requested here like the residual (clamped: row 0 for the threads
+  // that do not write; a slot is < G whatever the column)
+  int x_slot = 0, x_adapter = -1;
+  float x_scale = 0.f;
+  if constexpr (EXT == 2) {
+    x_slot = ((blockIdx.x * NB + cw0) / x.R) % x.G;
+    x_adapter = x.row_adapter[writer ? m0 + ml : 0];
+    x_scale = x.slot_scale[x_slot];
+  }
+
   f32x4 acc[MB][NBT];
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
@@ -153,6 +188,52 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16* __rest
 #pragma unroll
           for (int e = 0; e < 8; ++e) ss[mb] += (float)xf[i][mb][e] * (float)xf[i][mb][e];
       }
+    }
+  }
+
+  if constexpr (EXT == 1) {
+    // the second operand pair: K2 / 32 chunks dealt to the waves as above, 8 / NW of them per batch (K2 is a multiple of 256: a
+    // wave's count is a multiple of that).  gate|up reads one T slice per column block (the gate's and the up's part).
+    constexpr int B2 = 8 / NW;
+    constexpr int NP = (MODE == 1) ? NBT : 1;  // T slices per workgroup
+    const int nc2 = x.K2 / (32 * NW);
+    unsigned toff[NP][MB], boff[NBT];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const int w0 = (MODE == 1) ? p * N + blockIdx.x * 16 : blockIdx.x * NB;  // first weight row of the block: it names the part
+      const unsigned tcol = (unsigned)((w0 / x.rows_per_part) * x.K2 + fg * 8);
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) {
+        const int m = m0 + mb * 16 + fi;
+        toff[p][mb] = (unsigned)((m < M) ? m : M - 1) * x.ldt + tcol;
+      }
+    }
+#pragma unroll
+    for (int nb = 0; nb < NBT; ++nb) {  // the weight row of woff[nb], clamped the same way
+      const int n = (MODE == 1) ? nb * N + blockIdx.x * 16 + fi : blockIdx.x * NB + nb * 16 + fi;
+      const int nmax = (MODE == 1) ? (nb + 1) * N - 1 : N - 1;
+      boff[nb] = (unsigned)(n < nmax ? n : nmax) * x.ldb + (unsigned)(fg * 8);
+    }
+    for (int c0 = 0; c0 < nc2; c0 += B2) {
+      bf16x8 bfr[B2][NBT], tfr[B2][NP][MB];
+#pragma unroll
+      for (int i = 0; i < B2; ++i) {
+        const unsigned k = (unsigned)((wave + NW * (c0 + i)) * 32);
+#pragma unroll
+        for (int nb = 0; nb < NBT; ++nb) bfr[i][nb] = *reinterpret_cast<const bf16x8*>(x.Bst + (boff[nb] + k));
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+#pragma unroll
+          for (int mb = 0; mb < MB; ++mb) tfr[i][p][mb] = *reinterpret_cast<const bf16x8*>(x.T + (toff[p][mb] + k));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < B2; ++i)
+#pragma unroll
+        for (int nb = 0; nb < NBT; ++nb)
+#pragma unroll
+          for (int mb = 0; mb < MB; ++mb)
+            acc[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[i][nb], tfr[i][MODE == 1 ? nb : 0][mb], acc[mb][nb], 0, 0, 0);
     }
   }
 
@@ -207,6 +288,9 @@ __global__ __launch_bounds__(NW * 64) void gemm_skinny_kernel(const bf16* __rest
       const float sg = (float)(bf16)mh_silu(g);
       outv[j] = (bf16)(sg * u);
     }
+  } else if constexpr (EXT == 2) {
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) outv[j] = (x_adapter == x_slot) ? (bf16)(x_scale * tot[j]) : (bf16)0.f;
   } else {
 #pragma unroll
     for (int j = 0; j < CPT; ++j) {
@@ -266,7 +350,7 @@ extern "C" int mh_gemm_skinny(const void* A, int64_t lda, const void* W, int64_t
 #define MH_SK4(MODE_, NBT_, NW_, GRID_, RSTD_, MB_, BCH_)                                                                  \
   gemm_skinny_kernel<MODE_, NBT_, NW_, RSTD_, MB_, BCH_><<<dim3((unsigned)(GRID_), (unsigned)gy), NW_ * 64, 0, st>>>(      \
       (const bf16*)A, lda, (const bf16*)W, ldw, (bf16*)C, ldc, (const bf16*)R, ldr, (int)M, (int)N, (int)K, norm_eps,      \
-      row_ids, res_ids, vec)
+      row_ids, res_ids, vec, SkinnyNoExt{})
 #define MH_SK3(MODE_, NBT_, NW_, GRID_, RSTD_, MB_)                                                                        \
   do {                                                                                                                    \
     const int ncw_ = (int)(K / (32 * NW_)); /* chunks per wave; batches of the largest of 8 / 4 / 1 that divides it */    \
@@ -337,4 +421,146 @@ extern "C" int mh_gemm_skinny_wide(const void* A, int64_t lda, const void* W, in
 #undef MH_SK4
   MH_LAUNCH_CHECK();
   return MH_OK;
+}
+
+// ---- the per-request LoRA forms (EXT 1 / 2 of the kernel) ----------------------------------------------------------------------
+// One launcher for 1 <= M <= 256: the tiling is chosen by the rules of the two entry points above (narrow up to 64 rows, wide
+// beyond), so the main loop of a projection is the same code, shape for shape, as without the second operand pair.
+namespace {
+
+struct SkinnyTiling {
+  int nbt, mb, gy, vec;
+};
+
+SkinnyTiling skinny_tiling(int mode, int64_t M, int64_t N, const void* C, int64_t ldc) {
+  SkinnyTiling t;
+  if (M <= 64) {
+    const int row_blocks = (int)((M + 15) / 16);
+    t.nbt = (mode == MH_SKINNY_GATEUP) ? 2 : (g_skinny_nbt == 1 || g_skinny_nbt == 2 ? g_skinny_nbt : (N >= 2048 ? 2 : 1));
+    const int col_tiles = (mode == MH_SKINNY_GATEUP) ? (int)((N + 15) / 16) : (int)((N + 16 * t.nbt - 1) / (16 * t.nbt));
+    int mb = g_skinny_mb;
+    if (mb != 1 && mb != 2 && mb != 4) {
+      const int groups = 256 / col_tiles;
+      mb = groups >= 4 ? 1 : (groups >= 2 ? 2 : 4);
+    }
+    if (mb > row_blocks) mb = row_blocks >= 4 ? 4 : (row_blocks >= 2 ? 2 : 1);
+    t.mb = mb;
+    t.gy = (row_blocks + mb - 1) / mb;
+  } else {
+    t.nbt = (mode == MH_SKINNY_GATEUP) ? 2 : (N >= 2048 ? 2 : 1);
+    t.mb = 4;
+    t.gy = (int)((M + 63) / 64);
+  }
+  const int group_bytes = ((mode == MH_SKINNY_GATEUP || t.nbt == 1) ? 4 : 8) * 2;
+  t.vec = (((uintptr_t)C % group_bytes) == 0 && (ldc * 2) % group_bytes == 0) ? 1 : 0;
+  return t;
+}
+
+template <int EXT>
+int skinny_ext_launch(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* R, int64_t ldr,
+                      int mode, float norm_eps, const int64_t* row_ids, const int64_t* res_ids, int64_t M, int64_t N, int64_t K,
+                      const SkinnyTiling& t, const SkinnyExt& x, hipStream_t st) {
+  const int mb = t.mb, gy = t.gy, nbt = t.nbt;
+#define MH_SKX4(MODE_, NBT_, NW_, GRID_, RSTD_, MB_, BCH_)                                                                   \
+  gemm_skinny_kernel<MODE_, NBT_, NW_, RSTD_, MB_, BCH_, EXT><<<dim3((unsigned)(GRID_), (unsigned)gy), NW_ * 64, 0, st>>>( \
+      (const bf16*)A, lda, (const bf16*)W, ldw, (bf16*)C, ldc, (const bf16*)R, ldr, (int)M, (int)N, (int)K, norm_eps, row_ids, \
+      res_ids, t.vec, x)
+  // (the batch rule of the entry points above; MH_SKX_SMALL_BATCH names the classes that take the next smaller batch because the
+  //  larger one spills: the wide launcher's one class, and those the second operand pair adds)
+#define MH_SKX3(MODE_, NBT_, NW_, GRID_, RSTD_, MB_)                                                                         \
+  do {                                                                                                                      \
+    const int ncw_ = (int)(K / (32 * NW_));                                                                                 \
+    if (ncw_ == 16 && (NBT_ + MB_) <= 2) MH_SKX4(MODE_, NBT_, NW_, GRID_, RSTD_, MB_, 16);                                   \
+    else if (ncw_ % 8 == 0 && (NBT_ + MB_) <= 6 && !(MH_SKX_SMALL_BATCH(MODE_, NBT_, NW_, RSTD_, MB_)))                      \
+      MH_SKX4(MODE_, NBT_, NW_, GRID_, RSTD_, MB_, 8);                                                                       \
+    else if (ncw_ % 4 == 0) MH_SKX4(MODE_, NBT_, NW_, GRID_, RSTD_, MB_, 4);                                                 \
+    else MH_SKX4(MODE_, NBT_, NW_, GRID_, RSTD_, MB_, 1);                                                                    \
+  } while (0)
+#define MH_SKX_SMALL_BATCH(MODE_, NBT_, NW_, RSTD_, MB_) ((MODE_) == 0 && (NBT_) == 2 && (NW_) == 8 && (RSTD_) && (MB_) == 4)
+#define MH_SKX2(MODE_, NBT_, NW_, GRID_, RSTD_)                                                                              \
+  do {                                                                                                                      \
+    if (mb == 1) MH_SKX3(MODE_, NBT_, NW_, GRID_, RSTD_, 1);                                                                 \
+    else if (mb == 2) MH_SKX3(MODE_, NBT_, NW_, GRID_, RSTD_, 2);                                                            \
+    else MH_SKX3(MODE_, NBT_, NW_, GRID_, RSTD_, 4);                                                                         \
+  } while (0)
+#define MH_SKX(MODE_, NBT_, NW_, GRID_)                                                                                     \
+  do {                                                                                                                      \
+    if constexpr (EXT == 2) MH_SKX2(MODE_, NBT_, NW_, GRID_, false);                                                         \
+    else if (norm_eps > 0.f) MH_SKX2(MODE_, NBT_, NW_, GRID_, true);                                                         \
+    else MH_SKX2(MODE_, NBT_, NW_, GRID_, false);                                                                            \
+  } while (0)
+  if constexpr (EXT == 1) {
+    if (mode == MH_SKINNY_GATEUP) {
+      MH_SKX(1, 2, 4, (N + 15) / 16);
+      MH_LAUNCH_CHECK();
+      return MH_OK;
+    }
+  }
+  if (nbt == 2 && N > 4096) MH_SKX(0, 2, 4, (N + 31) / 32);
+  else if (nbt == 2) MH_SKX(0, 2, 8, (N + 31) / 32);
+  else MH_SKX(0, 1, 8, (N + 15) / 16);
+#undef MH_SKX
+#undef MH_SKX2
+#undef MH_SKX3
+#undef MH_SKX4
+#undef MH_SKX_SMALL_BATCH
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+}  // namespace
+
+extern "C" int mh_gemm_skinny_ext(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, const void* R,
+                                  int64_t ldr, const void* T, int64_t ldt, const void* Bst, int64_t ldb, int mode, float norm_eps,
+                                  const int64_t* row_ids, const int64_t* res_ids, int64_t M, int64_t N, int64_t K, int64_t K2,
+                                  int parts, int dtype, void* stream) {
+  MH_REQUIRE(dtype == MH_BF16, "gemm_skinny_ext: bf16 only");
+  MH_REQUIRE(M > 0 && M <= 256 && N > 0 && N < (1 << 24), "gemm_skinny_ext: needs 1 <= M <= 256 rows (M=%ld N=%ld)", (long)M, (long)N);
+  MH_REQUIRE(mode == MH_SKINNY_PLAIN || mode == MH_SKINNY_GATEUP, "gemm_skinny_ext: mode %d", mode);
+  MH_REQUIRE(K > 0 && K % 256 == 0 && K < (1 << 24), "gemm_skinny_ext: K=%ld must be a multiple of 256", (long)K);
+  MH_REQUIRE(K2 > 0 && K2 % 256 == 0 && K2 < (1 << 24), "gemm_skinny_ext: K2=%ld must be a multiple of 256", (long)K2);
+  MH_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0,
+             "gemm_skinny_ext: A/W rows must be 16-byte aligned");
+  MH_REQUIRE(T != nullptr && Bst != nullptr && ldt % 8 == 0 && ldb % 8 == 0 && ((uintptr_t)T & 15) == 0 && ((uintptr_t)Bst & 15) == 0,
+             "gemm_skinny_ext: T/Bst rows must be 16-byte aligned");
+  MH_REQUIRE(mode != MH_SKINNY_GATEUP || R == nullptr, "gemm_skinny_ext: the gate|up epilogue takes no residual");
+  const int64_t wrows = mode == MH_SKINNY_GATEUP ? 2 * N : N;
+  MH_REQUIRE(parts >= 1 && parts <= 64 && wrows % parts == 0 && ldt >= (int64_t)parts * K2 && ldb >= K2,
+             "gemm_skinny_ext: parts=%d must divide the %ld weight rows, T rows hold parts*K2 and Bst rows K2 values", parts, (long)wrows);
+  const int64_t Mcap = M <= 64 ? 64 : 256;
+  MH_REQUIRE(wrows * ldw < (int64_t(1) << 31) && Mcap * lda < (int64_t(1) << 31) && Mcap * ldc < (int64_t(1) << 31) &&
+                 (R == nullptr || Mcap * ldr < (int64_t(1) << 31)) && lda < (int64_t(1) << 24) && ldr < (int64_t(1) << 24) &&
+                 wrows * ldb < (int64_t(1) << 31) && Mcap * ldt < (int64_t(1) << 31),
+             "gemm_skinny_ext: operands too large for 32-bit element offsets");
+  const SkinnyTiling t = skinny_tiling(mode, M, N, C, ldc);
+  // a workgroup's column block reads ONE slice of T (gate|up: one per half): no part boundary inside it
+  const int64_t rpp = wrows / parts;
+  const bool whole = mode == MH_SKINNY_GATEUP ? (parts == 1 || (N % rpp == 0 && rpp % 16 == 0) || rpp == N) : (parts == 1 || rpp % (16 * t.nbt) == 0);
+  MH_REQUIRE(whole, "gemm_skinny_ext: a part boundary (every %ld weight rows) falls inside a %d-column block", (long)rpp,
+             mode == MH_SKINNY_GATEUP ? 16 : 16 * t.nbt);
+  SkinnyExt x{};
+  x.T = (const bf16*)T, x.Bst = (const bf16*)Bst, x.ldt = (unsigned)ldt, x.ldb = (unsigned)ldb, x.K2 = (int)K2, x.rows_per_part = (int)rpp;
+  return skinny_ext_launch<1>(A, lda, W, ldw, C, ldc, R, ldr, mode, norm_eps, row_ids, res_ids, M, N, K, t, x, (hipStream_t)stream);
+}
+
+extern "C" int mh_lora_shrink_rows(const void* A, int64_t lda, const void* W, int64_t ldw, void* T, int64_t ldt,
+                                   const int32_t* row_adapter, const float* slot_scale, const int64_t* row_ids, int64_t M,
+                                   int64_t K, int G, int R, int parts, int dtype, void* stream) {
+  MH_REQUIRE(dtype == MH_BF16, "lora_shrink_rows: bf16 only");
+  MH_REQUIRE(G >= 1 && R >= 8 && R % 8 == 0 && parts >= 1 && (int64_t)parts * G * R < (1 << 24),
+             "lora_shrink_rows: needs G >= 1 slots of a rank R that is a multiple of 8 (G=%d R=%d parts=%d)", G, R, parts);
+  const int64_t N = (int64_t)parts * G * R;
+  MH_REQUIRE(M > 0 && M <= 256, "lora_shrink_rows: needs 1 <= M <= 256 rows (M=%ld)", (long)M);
+  MH_REQUIRE(K > 0 && K % 256 == 0 && K < (1 << 24), "lora_shrink_rows: K=%ld must be a multiple of 256", (long)K);
+  MH_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && ((uintptr_t)A & 15) == 0 && ((uintptr_t)W & 15) == 0,
+             "lora_shrink_rows: A/W rows must be 16-byte aligned");
+  MH_REQUIRE(row_adapter != nullptr && slot_scale != nullptr && T != nullptr && ldt >= N, "lora_shrink_rows: row_adapter, slot_scale, T");
+  const int64_t Mcap = M <= 64 ? 64 : 256;
+  MH_REQUIRE(N * ldw < (int64_t(1) << 31) && Mcap * lda < (int64_t(1) << 31) && Mcap * ldt < (int64_t(1) << 31) && lda < (int64_t(1) << 24),
+             "lora_shrink_rows: operands too large for 32-bit element offsets");
+  const SkinnyTiling t = skinny_tiling(MH_SKINNY_PLAIN, M, N, T, ldt);
+  SkinnyExt x{};
+  x.row_adapter = row_adapter, x.slot_scale = slot_scale, x.G = G, x.R = R;
+  return skinny_ext_launch<2>(A, lda, W, ldw, T, ldt, nullptr, 0, MH_SKINNY_PLAIN, 0.f, row_ids, nullptr, M, N, K, t, x,
+                              (hipStream_t)stream);
 }

@@ -145,7 +145,8 @@ def graphs_enabled(device: torch.device) -> bool:
 class DecodeSession:
     def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int, shared_capacity: int = 0,
                  ragged: bool = False, row_params: bool = False, seeded: bool = False, prefix_slots: int = 0,
-                 prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False):
+                 prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False, lora_slots: int = 0,
+                 lora_rank: int = 64):
         tok = model.tokenizer
         self.model, self.B, self.cap, self.temp = model, B, capacity, float(temp)
         self.top_p, self.top_k = float(top_p), int(top_k)
@@ -156,8 +157,13 @@ class DecodeSession:
         self.prefix_slots, self.prefix_capacity = int(prefix_slots), int(prefix_capacity)
         self.kv_dtype = kv_dtype
         self.logprobs = bool(logprobs)
-        self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params, seeded,
-                                 prefix_slots, prefix_capacity, kv_dtype, logprobs)
+        self.lora_slots, self.lora_rank = int(lora_slots), int(lora_rank)
+        if lora_slots:  # (the call without the option is the call it was)
+            self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params, seeded,
+                                     prefix_slots, prefix_capacity, kv_dtype, logprobs, lora_slots, lora_rank)
+        else:
+            self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params, seeded,
+                                     prefix_slots, prefix_capacity, kv_dtype, logprobs)
         dev, dt = model.device, model.dtype
         self.T, self.V, self.Vp = tok.max_token_seq, tok.vocab_size, model.vocab_padded
         spec, tspec = model._specs["net"], model._specs["net_token"]
@@ -224,6 +230,11 @@ class DecodeSession:
         self.logits = torch.zeros((B, self.Vp), dtype=dt, device=dev)
         # RMSNorm weights folded into the projections that follow them (one launch for norm + projection)
         self.fold1 = self.fold2 = self.lm_fold = None
+        # (lora_slots) G adapter slots per stack, unmerged in the decode step (engine.LoraStack); one row_adapter / slot_scale for both
+        self.lora1 = self.lora2 = self.row_adapter = None
+        self._lora_loaded = {}      # slot -> (event-level layers, scale): what admit() merges for the prompt's prefill
+        self._merged = None         # the second copy of the event-level matrices, W + s B A of slot _merged_of
+        self._merged_of = None
         probe = torch.empty((B, 1), dtype=dt, device=dev)
         # 65 to 256 rows: the same folded layer on mh_gemm_skinny_wide, unless MH_DECODE_WIDE=0 (read here, once) keeps the general form
         self.wide = ops.decode_wide_enabled() and ops.skinny_wide_ok(probe, spec.D)
@@ -233,7 +244,15 @@ class DecodeSession:
             self.fold1 = engine.fold_norm_weights(model._W["net"])
             self.fold2 = engine.fold_norm_weights(model._W["net_token"])
             self.lm_fold = torch.empty_like(model.lm_head.weight.data)
+            if self.lora_slots:
+                self.lora1 = engine.LoraStack(spec, len(model._W["net"].layers), self.lora_slots, self.lora_rank, B, model._flat)
+                self.lora2 = engine.LoraStack(tspec, len(model._W["net_token"].layers), self.lora_slots, self.lora_rank, B, model._flat)
+                self.lora2.row_adapter, self.lora2.slot_scale = self.lora1.row_adapter, self.lora1.slot_scale
+                self.row_adapter = self.lora1.row_adapter
             self.refresh()
+        if self.lora_slots and self.lora1 is None:
+            raise ValueError("DecodeSession: lora_slots needs the fused folded decode form (hidden and MLP widths that are multiples of "
+                             "256, MH_DECODE_FOLD not 0)")
         self.g_net = None
         self.g_tok: List[Optional[torch.cuda.CUDAGraph]] = [None] * self.T
         self.g_noise = self.g_steps = None
@@ -256,7 +275,17 @@ class DecodeSession:
 
     @staticmethod
     def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False, row_params=False, seeded=False,
-                 prefix_slots=0, prefix_capacity=0, kv_dtype=None, logprobs=False):
+                 prefix_slots=0, prefix_capacity=0, kv_dtype=None, logprobs=False, lora_slots=0, lora_rank=64):
+        if lora_slots:
+            if not (ragged and row_params):
+                raise ValueError("DecodeSession: lora_slots is a form of the per-row session -- it needs ragged=True, row_params=True")
+            if model._flat.dtype != torch.bfloat16 or B > 256:
+                raise ValueError(f"DecodeSession: lora_slots needs a bf16 model and at most 256 rows (the skinny projections are the "
+                                 f"one form that takes the second operand pair): {model._flat.dtype}, {B} rows")
+            if int(lora_slots) != lora_slots or int(lora_rank) != lora_rank or lora_slots < 1 or lora_rank < 8 or lora_rank % 8 \
+                    or (lora_slots * lora_rank) % 256:
+                raise ValueError(f"DecodeSession: lora_slots={lora_slots!r}, lora_rank={lora_rank!r} -- the rank a multiple of 8 and "
+                                 f"slots x rank a multiple of 256")
         if logprobs and not (ragged and row_params):
             raise ValueError("DecodeSession: logprobs is a form of the per-row session -- it needs ragged=True, row_params=True")
         if kv_dtype is not None:
@@ -293,6 +322,8 @@ class DecodeSession:
                 form += (("kv", "fp8"),)
             if logprobs:  # (likewise, at the end: only a session whose samplers write log-probabilities carries it)
                 form += (("logp",),)
+            if lora_slots:  # (likewise)
+                form += (("lora", int(lora_slots), int(lora_rank)),)
             return (model._flat.data_ptr(), model._flat.dtype, B, capacity, form)
         key = (model._flat.data_ptr(), model._flat.dtype, B, capacity, float(temp), float(top_p), int(top_k))
         if ragged:
@@ -311,6 +342,10 @@ class DecodeSession:
         engine.fold_norm_weights(m._W["net_token"], out=self.fold2)
         lm_w = m.lm_head.weight.data
         self.lm_fold.copy_(lm_w.float() * m._W["net_token"].norm.float()[None, :])
+        if self.lora1 is not None:  # the norm-folded A stacks follow the norm weights; the merged copy follows the base weights
+            self.lora1.refresh(m._W["net"])
+            self.lora2.refresh(m._W["net_token"])
+            self._merged_of = None
 
     # ---- the step bodies (run eagerly, or once under capture) ---------------------------------------------
     def _net_body(self):
@@ -323,8 +358,12 @@ class DecodeSession:
             if self.kvs is not None:  # ... and behind the prompt of its slot, if it names one
                 from .ops_share import SlotPrefix
                 sh = SlotPrefix(self.kvs, self.slot_len, self.row_slot, self.ws)
-            engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, folded=self.fold1, out=self.hidden, row_pos=self.pos,
-                                wide=self.wide, shared=sh)
+            if self.lora1 is not None:
+                engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, folded=self.fold1, out=self.hidden, row_pos=self.pos,
+                                    wide=self.wide, shared=sh, lora=self.lora1)
+            else:
+                engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, folded=self.fold1, out=self.hidden, row_pos=self.pos,
+                                    wide=self.wide, shared=sh)
             self.pos.add_(1)
             torch.minimum(self.pos, self.pos_limit, out=self.pos)
             return
@@ -348,12 +387,13 @@ class DecodeSession:
         lm_w = m.lm_head.weight.data
         skinny = ops.gemm_skinny_wide if self.wide else ops.gemm_skinny
         if self.lm_fold is not None:  # the stack's final RMSNorm rides on the lm_head projection
+            more = dict(lora=self.lora2) if self.lora2 is not None else {}
             if i == 0:
                 h = engine.stack_decode(tspec, Wt, self.hidden, self.rope2, self.kv2, folded=self.fold2, final_norm=False,
-                                        wide=self.wide)
+                                        wide=self.wide, **more)
             else:  # the embedding of the token just sampled is looked up inside the first projections
                 h = engine.stack_decode(tspec, Wt, Wt.embed, self.rope2, self.kv2, folded=self.fold2, final_norm=False,
-                                        x_ids=self.samples_in, wide=self.wide)
+                                        x_ids=self.samples_in, wide=self.wide, **more)
             skinny(h, self.lm_fold, self.logits[:, : self.V], norm_eps=tspec.eps)
         else:
             x = self.hidden if i == 0 else Wt.embed.index_select(0, self.samples_in)
@@ -488,6 +528,58 @@ class DecodeSession:
             self.slot_len.zero_()
             self.row_slot.fill_(-1)
             self._reset_slots_host()
+        if self.row_adapter is not None:  # no row names an adapter and every slot is empty: nothing outlives the session's user
+            self.row_adapter.fill_(-1)
+            for g in list(self._lora_loaded):
+                self.unload_adapter(g)
+
+    def load_adapter(self, slot: int, layers_net, layers_tok, scale: float) -> None:
+        """(lora_slots) adapter slot ``slot`` <- one adapter: per stack a list over its layers of {target module: (A [r, in], B [out,
+        r])} and the scale alpha / r.  Stream-ordered copies into the fixed buffers the captured graphs read, zero-padded for r < R
+        and for targets the adapter lacks, then the norm fold of the A stacks.  ``ValueError`` before any copy: no such slot, a rank
+        above R, an unknown target."""
+        if self.lora1 is None:
+            raise ValueError("DecodeSession.load_adapter: not a lora_slots session")
+        self.lora1.check_slot(slot, layers_net)
+        self.lora2.check_slot(slot, layers_tok)
+        m = self.model
+        self.lora1.load_slot(slot, layers_net, scale)
+        self.lora2.load_slot(slot, layers_tok, scale)
+        self.lora1.refresh(m._W["net"])
+        self.lora2.refresh(m._W["net_token"])
+        self._lora_loaded[slot] = (layers_net, float(scale))
+        if self._merged_of == slot:
+            self._merged_of = None
+
+    def unload_adapter(self, slot: int) -> None:
+        """(lora_slots) empty slot ``slot``: zeros in its blocks of the stacks, scale 0"""
+        if self.lora1 is None or not 0 <= slot < self.lora_slots:
+            raise ValueError(f"DecodeSession.unload_adapter: slot {slot!r}")
+        self.load_adapter(slot, [{} for _ in self.lora1.a], [{} for _ in self.lora2.a], 0.0)
+        del self._lora_loaded[slot]
+
+    def _merged_weights(self, slot: int):
+        """the event-level matrices with adapter ``slot`` merged, W + s B A per target by ops.gemm_nt as LoraAdapter.materialize
+        does it, in a second copy of those matrices (allocated at the first adapted admission, re-materialised when the adapter
+        or the base weights change)"""
+        W = self.model._W["net"]
+        if self._merged is None:
+            self._merged = engine.StackTensors(embed=W.embed, norm=W.norm, layers=[
+                engine.LayerTensors(wqkv=torch.empty_like(lw.wqkv), wo=torch.empty_like(lw.wo), wgu=torch.empty_like(lw.wgu),
+                                    wd=torch.empty_like(lw.wd), n1=lw.n1, n2=lw.n2) for lw in W.layers])
+        if self._merged_of != slot:
+            layers, scale = self._lora_loaded[slot]
+            names = {"qkv": "wqkv", "o": "wo", "gu": "wgu", "d": "wd"}
+            for lw, lm, mods in zip(W.layers, self._merged.layers, layers):
+                for nm in names.values():
+                    getattr(lm, nm).copy_(getattr(lw, nm))
+                for t, (A, Bm) in mods.items():
+                    proj, part = engine.LORA_PROJ[t]
+                    n = Bm.shape[0]
+                    base, out = getattr(lw, names[proj])[part * n:(part + 1) * n], getattr(lm, names[proj])[part * n:(part + 1) * n]
+                    ops.gemm_nt(Bm, A, out, K=A.shape[0], alpha=scale, beta=1.0, res=base, tb=True)
+            self._merged_of = slot
+        return self._merged
 
     def _reset_slots_host(self) -> None:
         """(prefix slots) the host's books: no row names a slot, every slot is empty and free"""
@@ -612,7 +704,7 @@ class DecodeSession:
         self.pos.copy_(plan.seq_start[1:] - plan.seq_start[:-1])
 
     def admit(self, rows, tokens: torch.Tensor, lengths, limits, temp, top_p, top_k, first_masks, bans, seeds=None,
-              slots=None) -> None:
+              slots=None, adapter=None) -> None:
         """(row_params) n new requests into rows ``rows`` of the running batch, between two events (the header has the stream-order
         argument).  tokens [M, T]: the n prompts laid end to end, prompt s of lengths[s] events; limits[s]: the position row
         rows[s] is parked at (its max_len); temp / top_p / top_k: n values; first_masks / bans: uint8 [n, V] (host).  ONE packed
@@ -628,6 +720,10 @@ class DecodeSession:
         (mh_kv_store_seqs_rows over the slot cache, the slot ids as the row map) and NOT into cache row rows[s], whose own cache
         starts empty behind it; ``row_slot[rows]`` = slots and ``slot_len[slots]`` = lengths travel in the same block (two more
         index_copy_ calls).  Without ``slots`` such a session sets ``row_slot[rows]`` = -1.
+        ``adapter`` (a lora_slots session; one loaded slot for the whole admission, or None): ``row_adapter[rows]`` = the slot (-1 for
+        None) travels in the same block, and the prompts are prefilled against that adapter's MERGED event-level weights
+        (``_merged_weights``; the unfolded forward) -- so the prompt's K/V come from W + s B A in bf16, which is how the reference
+        serves an adapter, and the decoded events from the unmerged form.
         Everything is checked on the host first; ``ValueError`` before any launch."""
         if not (self.ragged and self.row_params):
             raise ValueError("DecodeSession.admit: rows are admitted into a ragged=True, row_params=True session only")
@@ -656,6 +752,9 @@ class DecodeSession:
             seed_vals = self._seed_values(seeds, n, "admit")
         elif seeds is not None:
             raise ValueError("admit: seeds are taken by a seeded=True session only")
+        if adapter is not None and (self.lora1 is None or isinstance(adapter, bool) or not isinstance(adapter, (int, np.integer))
+                                    or adapter not in self._lora_loaded):
+            raise ValueError(f"admit: adapter {adapter!r} -- a loaded slot of a lora_slots session (loaded: {sorted(self._lora_loaded)})")
         slot_ids = None
         if slots is not None:
             if self.kvs is None:
@@ -675,6 +774,8 @@ class DecodeSession:
                     (np.uint8, first_masks.numpy().reshape(-1)), (np.uint8, bans.numpy().reshape(-1))]
         if self.seeded:
             sections.append((np.int64, seed_vals))
+        if self.lora1 is not None:  # (| adapter i32)
+            sections.append((np.int32, [-1 if adapter is None else int(adapter)] * n))
         if slot_ids is not None:  # (| slots i64 | slots i32), behind everything a session without slots stages
             sections += [(np.int64, slot_ids), (np.int32, slot_ids)]
         dev = m.device
@@ -685,13 +786,12 @@ class DecodeSession:
         plan = ops.attn_seq_plan(lengths, spec.H).upload(dev)
         e = torch.empty((M, spec.D), dtype=m.dtype, device=dev)
         ops.embed_sum_fwd(tokens.to(dev).contiguous(), m._W["net"].embed, e)
+        Wp, foldp = (m._W["net"], self.fold1) if adapter is None else (self._merged_weights(int(adapter)), None)
         if slot_ids is not None:  # the prompts' K/V into their slots; the rows' own caches start empty behind them
             slot_idx, slots_dev = more_dev[-2:]
-            y = engine.stack_prefill_seqs(spec, m._W["net"], e, plan, self.rope1, self.kvs, folded=self.fold1, rows=slot_ids,
-                                          rows_dev=slots_dev)
+            y = engine.stack_prefill_seqs(spec, Wp, e, plan, self.rope1, self.kvs, folded=foldp, rows=slot_ids, rows_dev=slots_dev)
         else:
-            y = engine.stack_prefill_seqs(spec, m._W["net"], e, plan, self.rope1, self.kv1, folded=self.fold1, rows=ids,
-                                          rows_dev=rows_dev)
+            y = engine.stack_prefill_seqs(spec, Wp, e, plan, self.rope1, self.kv1, folded=foldp, rows=ids, rows_dev=rows_dev)
         # ---- the rows' state
         self.hidden.index_copy_(0, idx, y.index_select(0, last))
         self.pos.index_copy_(0, idx, len_dev)
@@ -703,6 +803,8 @@ class DecodeSession:
         self.ban.index_copy_(0, idx, ban_dev.view(n, V))
         if self.seeded:
             self.seed_rows.index_copy_(0, idx, seed_dev[0])
+        if self.lora1 is not None:
+            self.row_adapter.index_copy_(0, idx, more_dev[1 if self.seeded else 0])
         if slot_ids is not None:
             self.row_slot.index_copy_(0, idx, slots_dev)
             self.slot_len.index_copy_(0, slot_idx, len_dev)
@@ -834,6 +936,8 @@ class DecodeSession:
         self.ban.index_copy_(0, idx, ban_dev.view(n, V))
         if self.seeded:
             self.seed_rows.index_copy_(0, idx, seed_dev[0])
+        if self.row_adapter is not None:  # a child keeps its parent's adapter: its K/V were computed under it
+            self.row_adapter.index_copy_(0, idx, self.row_adapter.index_select(0, from_idx))
         if self.kvs is not None:
             self.row_slot.index_copy_(0, idx, more_dev[1 if self.seeded else 0])
             for d, g in zip(dst, src_slot):
@@ -872,6 +976,8 @@ class DecodeSession:
         idx = torch.tensor(ids, dtype=torch.int64).to(self.model.device)
         self.pos.index_fill_(0, idx, 0)
         self.pos_limit.index_fill_(0, idx, 0)
+        if self.row_adapter is not None:
+            self.row_adapter.index_fill_(0, idx, -1)
         if self.kvs is not None:
             self.row_slot.index_fill_(0, idx, -1)
             emptied = []

@@ -763,9 +763,75 @@ class _FoldList(list):
     jobs = None
 
 
+LORA_PROJ = {"q_proj": ("qkv", 0), "k_proj": ("qkv", 1), "v_proj": ("qkv", 2), "o_proj": ("o", 0), "gate_proj": ("gu", 0),
+             "up_proj": ("gu", 1), "down_proj": ("d", 0)}   # target module -> (projection of the fused layer, its part)
+
+
+class LoraStack:
+    """G slots of rank-R LoRA adapters for the decode step of ONE decoder stack, unmerged (stack_decode(lora=...)): a row's
+    projection is x W^T + s (x A^T) B^T with A, B, s of the slot row_adapter[b] names, -1 for none (peft's LoraLayer.forward
+    without dropout).  Per layer and fused projection (q|k|v 3 parts, o 1, gate|up 2, down 1) the slots' A matrices are stacked
+    [part][slot][R] along the rows and their B matrices [slot][R] along the columns, in fixed buffers a captured graph reads;
+    a slot that holds no adapter, the rows of a rank below R and the targets an adapter lacks are zeros.  The A stacks in front
+    of q|k|v and gate|up are kept twice: as loaded, and with the layer's RMSNorm weight folded in (``refresh``), as
+    fold_norm_weights does for W -- the shrink then runs on the unnormalised rows and the consumer's row scale covers it."""
+
+    def __init__(self, spec: StackSpec, n_layers: int, G: int, R: int, B: int, like: torch.Tensor):
+        if G < 1 or R < 8 or R % 8 or (G * R) % 256:
+            raise ValueError(f"LoraStack: {G} slots of rank {R}: the rank must be a multiple of 8 and slots x rank one of 256")
+        if like.dtype != torch.bfloat16 or not (1 <= B <= 256):
+            raise ValueError(f"LoraStack: the unmerged decode form is bf16 with at most 256 rows ({B} rows of {like.dtype})")
+        self.G, self.R, self.B = G, R, B
+        D, I, GR = spec.D, spec.I, G * R
+        z = lambda *shape: torch.zeros(shape, dtype=like.dtype, device=like.device)  # noqa: E731
+        self.a = [dict(qkv=z(3 * GR, D), o=z(GR, D), gu=z(2 * GR, D), d=z(GR, I)) for _ in range(n_layers)]
+        self.b = [dict(qkv=z(3 * D, GR), o=z(D, GR), gu=z(2 * I, GR), d=z(D, GR)) for _ in range(n_layers)]
+        self.a_n = [(z(3 * GR, D), z(2 * GR, D)) for _ in range(n_layers)]
+        self.slot_scale = torch.zeros(G, dtype=torch.float32, device=like.device)
+        self.row_adapter = torch.full((B,), -1, dtype=torch.int32, device=like.device)
+        self.dirty = True   # the norm-folded A stacks do not follow the raw ones yet: stack_decode refuses until ``refresh``
+
+    def check_slot(self, g: int, layers) -> None:
+        """the ValueErrors of ``load_slot``, and nothing else"""
+        G, R = self.G, self.R
+        if not 0 <= g < G or len(layers) != len(self.a):
+            raise ValueError(f"LoraStack.load_slot: slot {g} of {G}, {len(layers)} layers of {len(self.a)}")
+        for mods in layers:
+            for name, (A, Bm) in mods.items():
+                if name not in LORA_PROJ:
+                    raise ValueError(f"LoraStack.load_slot: unknown target module {name!r}")
+                if A.shape[0] > R or Bm.shape[1] != A.shape[0]:
+                    raise ValueError(f"LoraStack.load_slot: rank {A.shape[0]} in slots of rank {R}")
+
+    def load_slot(self, g: int, layers, scale: float) -> None:
+        """slot g <- one adapter: ``layers`` [n_layers] of {target module: (A [r, in], B [out, r])}, r <= R; stream-ordered
+        copies into the fixed buffers.  The stack is ``dirty`` until ``refresh`` has re-derived the folded A stacks."""
+        self.check_slot(g, layers)
+        G, R = self.G, self.R
+        self.dirty = True
+        for la, lb, mods in zip(self.a, self.b, layers):
+            for name, (proj, part) in LORA_PROJ.items():
+                rows = la[proj][(part * G + g) * R:(part * G + g + 1) * R]
+                out = lb[proj].shape[0] // (3 if proj == "qkv" else 2 if proj == "gu" else 1)
+                cols = lb[proj][part * out:(part + 1) * out, g * R:(g + 1) * R]
+                rows.zero_()
+                cols.zero_()
+                if name in mods:
+                    A, Bm = mods[name]
+                    rows[:A.shape[0]].copy_(A)
+                    cols[:, :A.shape[0]].copy_(Bm)
+        self.slot_scale[g:g + 1].fill_(float(scale))
+
+    def refresh(self, W: StackTensors) -> None:
+        """re-derive the norm-folded A stacks from the raw ones and the live RMSNorm weights"""
+        fake = StackTensors(layers=[LayerTensors(wqkv=la["qkv"], wgu=la["gu"], n1=lw.n1, n2=lw.n2) for la, lw in zip(self.a, W.layers)])
+        fold_norm_weights(fake, self.a_n)
+        self.dirty = False
+
+
 def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTable, kv: KVState, pos_dev=None,
                  folded=None, final_norm: bool = True, x_ids=None, out: Optional[torch.Tensor] = None, shared=None,
-                 row_pos=None, wide: Optional[bool] = None):
+                 row_pos=None, wide: Optional[bool] = None, lora: Optional[LoraStack] = None):
     """x [B, D]: one new position per sequence at index kv.len (q_len == 1 => no causal mask,
     TF:integrations/sdpa_attention.py:120).
 
@@ -796,7 +862,11 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
     attention step of every form of the layer is the two launches of ops_share.py (attn_prefix_partial_slots,
     attn_decode_append_rows_shared: +1 launch per layer against the fused per-row form, for every row, sharing or not).
     ``kv`` a ``KVStateQ`` (DecodeSession(kv_dtype="fp8")): ``row_pos`` without ``shared`` in the fused layer forms only (bf16, at most
-    256 rows) -- the attention step is mh_attn_decode_append_rows_fp8, same launch count; ``ValueError`` before any launch otherwise."""
+    256 rows) -- the attention step is mh_attn_decode_append_rows_fp8, same launch count; ``ValueError`` before any launch otherwise.
+    ``lora`` (a LoraStack whose ``refresh`` followed the last load): an adapter per row, unmerged -- the fused folded form only
+    (bf16, at most 256 rows, ``folded`` given), ``ValueError`` before any launch otherwise.  Each of the layer's four projections is
+    preceded by its shrink (mh_lora_shrink_rows) and takes the expand as a second operand pair (mh_gemm_skinny_ext): 9 launches per
+    layer.  The attention step, whichever form it has, is untouched."""
     _check_heads(spec)
     B, D = (x_ids.shape[0], x.shape[1]) if x_ids is not None else x.shape
     assert x_ids is None or folded is not None
@@ -841,9 +911,6 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
                                    pre_len_dev, pos_dev)
             sp.attn_decode_append_shared(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], ws, o, B, H, hd, kv.cap, kvp.cap, pre, pos,
                                          spec.scale, pre_len_dev, pos_dev)
-    if pos_dev is None and row_pos is None:
-        kv.reserve((pos if shared is None else kv.len) + 1)
-        rope.ensure(pos + 1)
     if wide is None:
         wide = ops.decode_wide_enabled()
     # (rows=B: with x_ids, x is the embedding table and the step has as many rows as there are ids)
@@ -855,7 +922,48 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
     if quant and not (fused and x.dtype == torch.bfloat16):
         raise ValueError(f"stack_decode: the fp8 K/V cache is served by the fused per-row attention only (bf16, at most 256 rows), "
                          f"not by the unfused kv_append_rows + attn_decode_rows pair: {B} rows of {x.dtype}")
+    if lora is not None:
+        if not (fused and folded is not None and x.dtype == torch.bfloat16 and ops.skinny_ext_ok(x, D, rows=B)
+                and ops.skinny_ext_ok(x, I, rows=B)):
+            raise ValueError(f"stack_decode: per-row LoRA adapters are served by the fused folded decode form only (bf16, at most 256 "
+                             f"rows, folded weights): {B} rows of {x.dtype}, folded {'given' if folded is not None else 'missing'}"
+                             + (" -- MH_DECODE_WIDE=0 (or wide=False) keeps 65 to 256 rows off that form" if B > 64 and not wide else ""))
+        if lora.B != B or len(lora.a) != len(W.layers):
+            raise ValueError(f"stack_decode: a LoraStack of {lora.B} rows and {len(lora.a)} layers for {B} rows and {len(W.layers)} layers")
+        if lora.dirty:
+            raise ValueError("stack_decode: the LoraStack was loaded into and not refreshed: its norm-folded A stacks are stale")
+    if pos_dev is None and row_pos is None:  # (behind every refusal: nothing is allocated for a call that is refused)
+        kv.reserve((pos if shared is None else kv.len) + 1)
+        rope.ensure(pos + 1)
     for li, lw in enumerate(W.layers):
+        if lora is not None:
+            wqkv_n, wgu_n = folded[li]
+            la, lb, (aq_n, agu_n) = lora.a[li], lora.b[li], lora.a_n[li]
+            G_, R_, ra, sc = lora.G, lora.R, lora.row_adapter, lora.slot_scale
+            ids = x_ids if li == 0 else None
+            t3 = _empty((B, 3 * G_ * R_), x)
+            ops.lora_shrink_rows(x, aq_n, t3, ra, sc, G_, R_, 3, row_ids=ids)
+            qkv = _empty((B, 3 * D), x)
+            ops.gemm_skinny_ext(x, wqkv_n, qkv, t3, lb["qkv"], 3, norm_eps=spec.eps, row_ids=ids)
+            o = _empty((B, D), x)
+            if attend is not None:
+                attend(qkv, o, li)
+            else:
+                ops.attn_decode_append(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, pos, spec.scale, pos_dev)
+            t1 = _empty((B, G_ * R_), x)
+            ops.lora_shrink_rows(o, la["o"], t1, ra, sc, G_, R_, 1)
+            x2 = _empty((B, D), x)
+            ops.gemm_skinny_ext(o, lw.wo, x2, t1, lb["o"], 1, res=x, res_ids=ids)
+            t2 = _empty((B, 2 * G_ * R_), x)
+            ops.lora_shrink_rows(x2, agu_n, t2, ra, sc, G_, R_, 2)
+            a = _empty((B, I), x)
+            ops.gemm_skinny_ext(x2, wgu_n, a, t2, lb["gu"], 2, mode=ops.SKINNY_GATEUP, norm_eps=spec.eps)
+            t1 = _empty((B, G_ * R_), x)
+            ops.lora_shrink_rows(a, la["d"], t1, ra, sc, G_, R_, 1)
+            x3 = _empty((B, D), x)
+            ops.gemm_skinny_ext(a, lw.wd, x3, t1, lb["d"], 1, res=x2)
+            x = x3
+            continue
         if fused and folded is not None:
             wqkv_n, wgu_n = folded[li]
             ids = x_ids if li == 0 else None  # layer 0 may read its input rows straight from the embedding table

@@ -127,3 +127,52 @@ class LoraAdapter:
                "bias": "none", "target_modules": list(self.target_modules), "fan_in_fan_out": False, "use_rslora": False}
         with open(os.path.join(directory, "adapter_config.json"), "w") as f:
             json.dump(cfg, f, indent=2)
+
+
+def adapter_layers(model, src):
+    """An adapter as the decode pool's slots take it (DecodeSession.load_adapter): ``src`` a directory in peft's layout, as
+    ``MIDIModel.load_merge_lora`` reads it (rsLoRA scaling included), or a ``LoraAdapter`` -> (layers of "net", layers of "net_token",
+    scale, r), a stack's layers being a list of {target module: (A [r, in], B [out, r])} on the model's device in its dtype.
+    ``ValueError`` for a target that is no q / k / v / o / gate / up / down projection of a decoder layer of this model."""
+    import re
+    from .engine import LORA_PROJ
+    if isinstance(src, LoraAdapter):
+        pairs = {name: (src.A[name], src.B[name]) for name, _, _, _ in src.targets}
+        scale, r = src.scale, src.r
+    else:
+        cfg_path = os.path.join(src, "adapter_config.json")
+        if not os.path.isdir(src) or not os.path.exists(cfg_path):
+            raise FileNotFoundError(f"{src}: not a local LoRA adapter directory")
+        with open(cfg_path) as f:
+            cfg = json.load(f)
+        if cfg.get("peft_type", "LORA") != "LORA" or cfg.get("fan_in_fan_out"):
+            raise ValueError(f"{src}: unsupported adapter (peft_type {cfg.get('peft_type')}, fan_in_fan_out {cfg.get('fan_in_fan_out')})")
+        r, alpha = int(cfg["r"]), float(cfg.get("lora_alpha", cfg["r"]))
+        scale = alpha / math.sqrt(r) if cfg.get("use_rslora") else alpha / r
+        st_path = os.path.join(src, "adapter_model.safetensors")
+        if os.path.exists(st_path):
+            from safetensors.torch import load_file
+            sd = load_file(st_path)
+        else:
+            sd = torch.load(os.path.join(src, "adapter_model.bin"), map_location="cpu")
+        pairs = {}
+        for key, a in sd.items():
+            if not key.endswith("lora_A.weight"):
+                continue
+            stem = key[: -len(".lora_A.weight")]
+            name = stem
+            for prefix in ("base_model.model.", "base_model."):
+                if name.startswith(prefix):
+                    name = name[len(prefix):]
+                    break
+            pairs[name] = (a, sd[stem + ".lora_B.weight"])
+    stacks = {k: [dict() for _ in model._W[k].layers] for k in ("net", "net_token")}
+    for name, (A, B) in pairs.items():
+        m = re.match(r"^(net|net_token)\.layers\.(\d+)\.(?:self_attn|mlp)\.(\w+)$", name)
+        if m is None or m.group(3) not in LORA_PROJ or int(m.group(2)) >= len(stacks[m.group(1)]):
+            raise ValueError(f"adapter target {name!r} is no q/k/v/o/gate/up/down projection of a decoder layer of this model")
+        if A.dim() != 2 or B.dim() != 2 or B.shape[1] != A.shape[0]:
+            raise ValueError(f"adapter target {name!r}: A {tuple(A.shape)}, B {tuple(B.shape)}")
+        stacks[m.group(1)][int(m.group(2))][m.group(3)] = (A.to(device=model.device, dtype=model.dtype).contiguous(),
+                                                            B.to(device=model.device, dtype=model.dtype).contiguous())
+    return stacks["net"], stacks["net_token"], float(scale), int(r)

@@ -866,7 +866,8 @@ class MIDIModel(nn.Module):
         return self._ragged_prompts([prompt], rp["max_len"], crop)[0], rp
 
     def decode_pool(self, rows: int, capacity: int, generator=None, seeded: bool = False, prefix_slots: int = 0,
-                    prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False):
+                    prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False, lora_slots: int = 0,
+                    lora_rank: int = 64):
         """(ours) a ``pool.DecodePool`` on this model: ``rows`` decode rows that requests are admitted into and released from
         while the batch runs (continuous batching).  ``capacity``: cache rows per decode row; a request needs
         max_len + 1 <= capacity (the session's own capacity is rounded up as every session's is, 256 x 2^k).  The pool takes one
@@ -879,8 +880,15 @@ class MIDIModel(nn.Module):
         ``kv_dtype="fp8"``: the rows' event-level K/V is cached as e4m3 codes with a scale per head and event, 0.53 x the bytes
         (pool.py "FP8 K/V"); a bf16 model, at most 256 rows, not with prefix slots (``ValueError``).
         ``logprobs=True``: ``pool.logprobs(rid)`` gives the model's log-likelihood of every event a request generated (pool.py
-        "LOG-LIKELIHOODS"); with any of the options above.  Nothing is launched here."""
+        "LOG-LIKELIHOODS"); with any of the options above.
+        ``lora_slots`` = G > 0 with ``lora_rank`` = R: the pool keeps G LoRA adapters of rank at most R beside the base weights
+        (``pool.load_adapter``) and ``submit(..., adapter=id)`` decodes a request under one of them, unmerged, in the same batch as
+        requests on other adapters and on none (pool.py "LORA ADAPTERS"); a bf16 model, at most 256 rows, G R a
+        multiple of 256 (``ValueError``); with any of the options above.  Nothing is launched here."""
         from .pool import DecodePool
+        if lora_slots:
+            return DecodePool(self, rows, capacity, generator, seeded, prefix_slots, prefix_capacity, kv_dtype=kv_dtype,
+                              logprobs=logprobs, lora_slots=lora_slots, lora_rank=lora_rank)
         if logprobs:
             return DecodePool(self, rows, capacity, generator, seeded, prefix_slots, prefix_capacity, kv_dtype=kv_dtype,
                               logprobs=True)
@@ -891,7 +899,8 @@ class MIDIModel(nn.Module):
         return DecodePool(self, rows, capacity, generator, seeded)
 
     def generate_pool(self, requests, rows: int, capacity: Optional[int] = None, generator=None,
-                      kv_dtype: Optional[str] = None, logprobs: bool = False) -> list:
+                      kv_dtype: Optional[str] = None, logprobs: bool = False, adapters: Optional[dict] = None,
+                      lora_rank: int = 64) -> list:
         """(ours) ``requests``: a list of dicts, each the keyword arguments of ``DecodePool.submit`` (``prompt`` and any of max_len,
         temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change, disable_channels, seed).  If EVERY request
         carries ``"seed"`` the pool is a seeded one; some with and some without is a ``ValueError``.  They are submitted in order
@@ -899,7 +908,9 @@ class MIDIModel(nn.Module):
         finishes is handed to the next request at once.  -> a list of ``np.ndarray (<= max_len, 8) int64``, request i's at index
         i, its prompt in front.  ``capacity`` defaults to the largest max_len + 1.  ``kv_dtype``: as ``decode_pool`` takes it.
         ``logprobs=True``: -> a list of ``(events, logprobs)`` pairs instead, ``logprobs`` the request's ``DecodePool.logprobs``
-        array (np.float32, one value per generated event, aligned with ``events[len(prompt):]``)."""
+        array (np.float32, one value per generated event, aligned with ``events[len(prompt):]``).
+        ``adapters`` = {name: src} (``src`` as ``DecodePool.load_adapter`` takes it): the pool gets a slot for each (as many of rank
+        ``lora_rank`` as make slots x rank a multiple of 256) and a request's ``"adapter": name`` decodes it under that adapter."""
         requests = list(requests)
         if not requests:
             return []
@@ -911,7 +922,18 @@ class MIDIModel(nn.Module):
         kvq = dict(kv_dtype=kv_dtype) if kv_dtype is not None else {}
         if logprobs:
             kvq["logprobs"] = True
+        if adapters:
+            per = 256 // math.gcd(256, int(lora_rank))   # slots come in steps that keep slots x rank a multiple of 256
+            kvq.update(lora_slots=-(-len(adapters) // per) * per, lora_rank=lora_rank)
+        elif any(r.get("adapter") is not None for r in requests):
+            raise ValueError("generate_pool: a request names an adapter and ``adapters`` is empty")
         with self.decode_pool(rows, capacity, generator, seeded=with_seed > 0, **kvq) as pool:
+            if adapters:
+                names = {name: pool.load_adapter(src) for name, src in adapters.items()}
+                unknown = [r["adapter"] for r in requests if r.get("adapter") is not None and r["adapter"] not in names]
+                if unknown:
+                    raise ValueError(f"generate_pool: requests name the adapters {unknown}; given: {sorted(names)}")
+                requests = [dict(r, adapter=names[r["adapter"]]) if r.get("adapter") is not None else r for r in requests]
             ids = [pool.submit(**r) for r in requests]
             while pool.pending():
                 pool.step()
@@ -964,8 +986,11 @@ class MIDIModel(nn.Module):
     # decode sessions: buffers + captured graphs, one per concurrent generate() call (decode.py)
     def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int, shared_need: int = 0,
                           ragged: bool = False, row_params: bool = False, seeded: bool = False, prefix_slots: int = 0,
-                          prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False):
-        """``logprobs`` (row_params only): the session whose samplers also write the drawn ids' log-probabilities (DecodeSession); a
+                          prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False, lora_slots: int = 0,
+                          lora_rank: int = 64):
+        """``lora_slots`` / ``lora_rank`` (row_params only): the session with that many LoRA adapter slots (DecodeSession); a pooled
+        session of its own kind, 0: the session as it was.
+        ``logprobs`` (row_params only): the session whose samplers also write the drawn ids' log-probabilities (DecodeSession); a
         pooled session of its own kind, False: the session as it was.
         ``kv_dtype`` = "fp8" (row_params only): the session whose event-level cache holds e4m3 codes and scales (DecodeSession); a
         pooled session of its own kind, None: the session as it was.
@@ -991,7 +1016,10 @@ class MIDIModel(nn.Module):
             pcap = 256
             while pcap < prefix_capacity:
                 pcap *= 2
-        if logprobs:
+        if lora_slots:
+            key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap,
+                                         kv_dtype, logprobs, lora_slots, lora_rank)
+        elif logprobs:
             key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap,
                                          kv_dtype, True)
         elif kv_dtype is not None:
@@ -1013,6 +1041,9 @@ class MIDIModel(nn.Module):
         if found is not None:
             found.refresh()  # weights may have been trained / merged since the session derived its folded copies
             return found
+        if lora_slots:
+            return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap, kv_dtype,
+                                 logprobs=logprobs, lora_slots=lora_slots, lora_rank=lora_rank)
         if logprobs:
             return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap, kv_dtype,
                                  logprobs=True)

@@ -621,9 +621,14 @@ _SHARE = ("attn_prefix_partial_slots", "attn_decode_append_rows_shared")
 _KVQ = ("kv_store_seqs_rows_fp8", "attn_decode_append_rows_fp8", "kv_fork_rows_fp8")
 # ... and the per-row and seeded samplers that also write the drawn id's log-probability (ops_logp.py; stand-ins in tests/emu_logp.py)
 _LOGP = ("sample_top_p_k_rows_logp", "sample_top_p_k_seeded_logp")
+# ... and the projections of a decode batch with a LoRA adapter per row (ops_lora.py)
+_LORA = ("lora_shrink_rows", "gemm_skinny_ext", "skinny_ext_ok")
 
 
 def __getattr__(name: str):
+    if name in _LORA:
+        from . import ops_lora
+        return getattr(ops_lora, name)
     if name in _LOGP:
         from . import ops_logp
         return getattr(ops_logp, name)

@@ -123,6 +123,24 @@ prompt; a held request keeps its array; a row handed to a later request starts e
 A pool made without ``logprobs`` takes the session, the graphs and the launches it took.  Measured: DESIGN 7.12
 (``tools/bench_pool_logp.py``, ``profiles/pool_logp_ab.txt``).
 
+LORA ADAPTERS.  ``model.decode_pool(rows, capacity, lora_slots=G, lora_rank=R)`` -- with any of the options above --
+runs on a session that keeps G adapter slots of rank R beside the base weights (27 MB an adapter at r = 64 for tv2o-medium, against
+467 MB for a merged copy), and ``submit(..., adapter=id)`` decodes a request under the adapter ``load_adapter(src)`` returned that id
+for: every row's projection is ``x W^T + s (x A^T) B^T`` with A, B, s of the row's own slot, unmerged (``mh_lora_shrink_rows`` ahead of
+each of a layer's four projections, the expand inside ``mh_gemm_skinny_ext``), so requests on different adapters and on none share one
+batch and one copy of the weights.  The stated limits:
+  * the PROMPT is prefilled against the adapter's MERGED event-level weights (W + s B A in bf16, a second copy of those matrices
+    that the session re-materialises when the adapter of an admission changes): the prompt's K/V come from the merged weights, which
+    is how the reference serves an adapter (``load_merge_lora``), and the decoded events come from the unmerged form.  The two differ
+    by bf16 roundings, as a merged bf16 model differs from float arithmetic on W + s B A;
+  * an admission is split into one ``admit`` per adapter, in the order the adapters first appear in it, so a request's admission
+    group is the requests on its own adapter admitted with it;
+  * a fork child keeps its parent's adapter (its K/V were computed under it); ``unload_adapter`` is refused while a queued,
+    running or held request names the adapter; adapters are never evicted on their own;
+  * every row of such a pool pays the four extra launches per layer, adapted or not (DESIGN 7.13 has the numbers);
+  * a bf16 model, at most 256 rows, ``G R`` a multiple of 256 (``ValueError`` at construction otherwise).
+A pool made without ``lora_slots`` takes the session, the graphs and the launches it took.
+
 Out of scope:
   * a background thread or server loop -- the caller owns the loop (and the thread: one pool, one thread);
   * shrinking the row caches of a pool with prefix slots, or a prompt shared ACROSS pools;
@@ -158,7 +176,7 @@ class _Request:
     #  group this request LEADS in the queue, 0 for the siblings behind it; kw: the settings as given, a child's defaults)
     #  share: the request continues a prompt that sits in a prefix slot -- a share_prefix submit, its siblings, their fork children)
     #  logp: ll of every event the request generated itself, beside ``events`` (a pool with logprobs=True; empty otherwise)
-    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done", "hold", "held", "eos", "group", "kw", "share", "logp")
+    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done", "hold", "held", "eos", "group", "kw", "share", "logp", "adapter")
 
     def __init__(self, prompt: np.ndarray, rp: dict, kw: dict, hold: bool = False, group: int = 1, share: bool = False):
         self.prompt, self.rp, self.max_len, self.kw, self.share = prompt, rp, rp["max_len"][0], kw, bool(share)
@@ -167,6 +185,7 @@ class _Request:
         self.row: Optional[int] = None
         self.done = False
         self.hold, self.held, self.eos, self.group = bool(hold), False, False, group
+        self.adapter: Optional[int] = None   # the adapter id the request decodes under (a pool with lora_slots)
 
 
 class DecodePool:
@@ -174,7 +193,8 @@ class DecodePool:
     kv_dtype, logprobs)``"""
 
     def __init__(self, model, rows: int, capacity: int, generator=None, seeded: bool = False, prefix_slots: int = 0,
-                 prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False):
+                 prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False, lora_slots: int = 0,
+                 lora_rank: int = 64):
         if int(rows) != rows or rows < 1 or int(capacity) != capacity or capacity < 2:
             raise ValueError(f"decode_pool: {rows} rows of capacity {capacity}")
         if kv_dtype is not None:
@@ -186,6 +206,16 @@ class DecodePool:
                 raise ValueError(f"decode_pool: kv_dtype=\"fp8\" needs a bf16 model and at most 256 rows: {model.dtype}, {rows} rows")
         self.kv_dtype = kv_dtype
         self.want_logprobs = bool(logprobs)
+        if lora_slots:
+            if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) for x in (lora_slots, lora_rank)) or lora_slots < 1 \
+                    or lora_rank < 8 or lora_rank % 8 or (lora_slots * lora_rank) % 256:
+                raise ValueError(f"decode_pool: lora_slots={lora_slots!r}, lora_rank={lora_rank!r} -- the rank a multiple of 8 and "
+                                 f"slots x rank a multiple of 256")
+            if rows > 256 or model.dtype != torch.bfloat16:
+                raise ValueError(f"decode_pool: lora_slots needs a bf16 model and at most 256 rows: {model.dtype}, {rows} rows")
+        self.lora_slots, self.lora_rank = int(lora_slots), int(lora_rank)
+        self.adapters: Dict[int, int] = {}               # adapter id -> the session's slot
+        self._next_adapter = 0
         if (prefix_slots or prefix_capacity) and not (
                 all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) for x in (prefix_slots, prefix_capacity))
                 and prefix_slots >= 1 and prefix_capacity >= 1):
@@ -207,7 +237,7 @@ class DecodePool:
 
     # ---- the caller's side ----------------------------------------------------------------------------------------------
     def submit(self, prompt, max_len=512, temp=1.0, top_p=0.98, top_k=20, ban_eos=False, disable_patch_change=False,
-               disable_control_change=False, disable_channels=None, seed=None, n=1, hold=False, share_prefix=False):
+               disable_control_change=False, disable_channels=None, seed=None, n=1, hold=False, share_prefix=False, adapter=None):
         """queue one request; -> its id.  Checked as ``generate_ragged`` checks a row with values of its own (the same code, the
         same ``ValueError``s), plus ``max_len + 1 > capacity``; the prompt is cropped to its last 4096 events, as the stream forms
         crop.  ``seed``: required in a seeded pool (an int in [0, 2^64)), refused in an unseeded one.  Nothing is launched here.
@@ -224,6 +254,9 @@ class DecodePool:
         ``ValueError``, before any launch: a pool without slots; a prompt of more than ``prefix_capacity`` events (after the crop)."""
         if self._closed:
             raise ValueError("DecodePool.submit: the pool is closed")
+        if adapter is not None and adapter not in self.adapters:
+            raise ValueError(f"DecodePool.submit: adapter {adapter!r} is not loaded in this pool (load_adapter returns the ids: "
+                             f"{sorted(self.adapters)})")
         if share_prefix and not self.prefix_slots:
             raise ValueError("DecodePool.submit: share_prefix needs a pool with prefix slots -- decode_pool(..., prefix_slots=G, "
                              "prefix_capacity=Pmax)")
@@ -242,8 +275,41 @@ class DecodePool:
             rids.append(self._next_id)
             self._next_id += 1
             self.requests[rids[-1]] = _Request(p, rp, kw, hold=hold, group=n if i == 0 else 0, share=share_prefix)
+            self.requests[rids[-1]].adapter = adapter
             self.queue.append(rids[-1])
         return rids[0] if n == 1 else rids
+
+    def load_adapter(self, src) -> int:
+        """(a pool made with ``lora_slots``) load one LoRA adapter into a free slot; -> its id, for ``submit(adapter=id)``.  ``src``: a
+        directory in peft's layout, as ``MIDIModel.load_merge_lora`` reads it (rsLoRA scaling as there), or a ``lora.LoraAdapter``.
+        Stream-ordered copies into the session's fixed buffers: rows that run are untouched.  ``ValueError`` before any copy: a pool
+        without slots, a rank above ``lora_rank``, a target that is no projection of a decoder layer, no free slot."""
+        from .lora import adapter_layers
+        if self._closed or not self.lora_slots:
+            raise ValueError("DecodePool.load_adapter: " + ("the pool is closed" if self._closed else
+                             "this pool has no adapter slots -- decode_pool(..., lora_slots=G, lora_rank=R)"))
+        net, tok, scale, r = adapter_layers(self.model, src)
+        if r > self.lora_rank or any(A.shape[0] > self.lora_rank for layers in (net, tok) for mods in layers for A, _ in mods.values()):
+            raise ValueError(f"DecodePool.load_adapter: an adapter of rank {r} in slots of rank {self.lora_rank}")
+        free = [g for g in range(self.lora_slots) if g not in self.adapters.values()]
+        if not free:
+            raise ValueError(f"DecodePool.load_adapter: all {self.lora_slots} adapter slots are taken -- unload_adapter one")
+        with torch.inference_mode():
+            self._session().load_adapter(free[0], net, tok, scale)
+        aid = self._next_adapter
+        self._next_adapter += 1
+        self.adapters[aid] = free[0]
+        return aid
+
+    def unload_adapter(self, aid: int) -> None:
+        """free the slot of adapter ``aid``; refused (``ValueError``) while a queued, running or held request names it"""
+        if self._closed or aid not in self.adapters:
+            raise ValueError(f"DecodePool.unload_adapter: no adapter {aid!r} in this pool")
+        users = [rid for rid, r in self.requests.items() if r.adapter == aid and (r.row is not None or rid in self.queue)]
+        if users:
+            raise ValueError(f"DecodePool.unload_adapter: adapter {aid} is named by requests {users} (queued, running or held)")
+        with torch.inference_mode():
+            self.ses.unload_adapter(self.adapters.pop(aid))
 
     def _seeds(self, seed, n: int, what: str, count_name: str) -> list:
         """the seed argument of submit(n=) / fork(count=) -> n seeds (None each in an unseeded pool); one request takes a scalar,
@@ -339,6 +405,7 @@ class DecodePool:
             rids.append(self._next_id)
             self._next_id += 1
             child = self.requests[rids[-1]] = _Request(p, one, kw, hold=hold, share=r.share)
+            child.adapter = r.adapter   # (the session's fork copies row_adapter with the row)
             child.row = row
             self.occupied[row] = rids[-1]
         return rids
@@ -395,6 +462,8 @@ class DecodePool:
                 slots = dict(kv_dtype=self.kv_dtype)
             if self.want_logprobs:  # (the call without the option is the call it was)
                 slots["logprobs"] = True
+            if self.lora_slots:  # (likewise)
+                slots.update(lora_slots=self.lora_slots, lora_rank=self.lora_rank)
             ses = self.model._checkout_session(self.rows, self.capacity, 1.0, 0.98, 1, ragged=True, row_params=True,
                                                 seeded=self.seeded, **slots)
             ses.reset()                      # every row free: pos = pos_limit = 0
@@ -432,17 +501,26 @@ class DecodePool:
         for share in (True, False):
             if not lead[share]:
                 continue
-            rows, rids = [r for r, _ in lead[share]], [i for _, i in lead[share]]
-            reqs = [self.requests[rid] for rid in rids]
-            rp = {name: [r.rp[name][0] for r in reqs] for name in reqs[0].rp}
-            first, ban = self.model._mask_rows(rp)
-            tokens = torch.from_numpy(np.concatenate([r.prompt for r in reqs], axis=0))
-            into = {"slots": ses.free_slots()[:len(rows)]} if share else {}
-            ses.admit(rows, tokens, [len(r.prompt) for r in reqs], rp["max_len"], rp["temp"], rp["top_p"], rp["top_k"], first, ban,
-                      seeds=rp.get("seed"), **into)
-            for row, rid, r in zip(rows, rids, reqs):
-                r.row = row
-                self.occupied[row] = rid
+            # ... and one admit per adapter, in the order the adapters first appear (a pool without adapter slots: one admit)
+            order = []
+            for _, i in lead[share]:
+                if self.requests[i].adapter not in order:
+                    order.append(self.requests[i].adapter)
+            for aid in order:
+                mine = [(r, i) for r, i in lead[share] if self.requests[i].adapter == aid]
+                rows, rids = [r for r, _ in mine], [i for _, i in mine]
+                reqs = [self.requests[rid] for rid in rids]
+                rp = {name: [r.rp[name][0] for r in reqs] for name in reqs[0].rp}
+                first, ban = self.model._mask_rows(rp)
+                tokens = torch.from_numpy(np.concatenate([r.prompt for r in reqs], axis=0))
+                into = {"slots": ses.free_slots()[:len(rows)]} if share else {}
+                if self.lora_slots:
+                    into["adapter"] = None if aid is None else self.adapters[aid]
+                ses.admit(rows, tokens, [len(r.prompt) for r in reqs], rp["max_len"], rp["temp"], rp["top_p"], rp["top_k"], first,
+                          ban, seeds=rp.get("seed"), **into)
+                for row, rid, r in zip(rows, rids, reqs):
+                    r.row = row
+                    self.occupied[row] = rid
         if forks:  # the siblings, right behind the prefills that made their leaders: the leaders' K/V and last hidden rows -- a
             #        sharing group's siblings JOIN the leader's slot instead and copy nothing
             sibs = [self.requests[rid] for _, _, rid, _ in forks]
