@@ -461,6 +461,24 @@ int mh_attn_decode_rows(const void* qkv, const void* kcache, const void* vcache,
 int mh_attn_decode_append_rows(const void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache, void* o,
                                int64_t B, int H, int hd, int64_t Lmax, float scale, const int32_t* row_pos, int dtype,
                                void* stream);
+/* The per-row pair THROUGH A ROW MAP (DecodeSession(lookahead=k): the rows of a group share the cache sequence of their leader).
+ * row_cache is a DEVICE int32 [B] beside row_pos: row b belongs to cache sequence row_cache[b] of a cache of n_cache sequences,
+ * kcache / vcache [n_cache, H, Lmax, hd]; a value outside [0, n_cache) marks the row INACTIVE.
+ *   mh_kv_append_rows_via: row b rotates its q and k at row_pos[b] (in qkv, as mh_kv_append_rows does) and stores K and V into
+ *     row row_pos[b] of cache sequence row_cache[b].  An inactive row, or one whose position lies outside [0, Lmax), writes nothing
+ *     and leaves its qkv row as it is.  Two rows of one cache sequence at one position is the caller's error (both write).
+ *   mh_attn_decode_rows_via: row b attends to rows [0, row_pos[b]] of cache sequence row_cache[b] (clamped as the per-row form
+ *     clamps); an inactive row writes zeros to its row of o.
+ * Launched as a pair, the append first: row j then sees the keys that the other rows of its cache sequence appended below its own
+ * position in the same pair.  The same kernels as mh_kv_append_rows / mh_attn_decode_rows (a template parameter): the loads, the
+ * loop, the masking and the merge in the same order, only the cache base address differs.  The refusals of those two, plus
+ * row_cache NULL and n_cache outside [1, 65535]: MH_ERR_ARG.                                                                     */
+int mh_kv_append_rows_via(void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache, int64_t B, int H, int hd,
+                          int64_t Lmax, const int32_t* row_pos, const int32_t* row_cache, int64_t n_cache, int dtype,
+                          void* stream);
+int mh_attn_decode_rows_via(const void* qkv, const void* kcache, const void* vcache, void* o, int64_t B, int H, int hd,
+                            int64_t Lmax, float scale, const int32_t* row_pos, const int32_t* row_cache, int64_t n_cache,
+                            int dtype, void* stream);
 /* Decode over a prompt that every row of the batch shares (MIDIModel.generate(share_prompt=True)); head_dim 64 only.
  * The prompt's K/V are cached once, kpre / vpre [H, Pmax, hd] (rows [0, pre_len) valid); each row keeps only its own suffix,
  * ksuf / vsuf [B, H, Lsuf, hd].  qkv [B, 3*H*hd] holds the UNROTATED q,k,v of absolute position `pos` and is left untouched.

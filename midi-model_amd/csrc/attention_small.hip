@@ -480,12 +480,22 @@ extern "C" int mh_tokattn_bwd_rows(const void* zc, const int64_t* ids, int64_t l
 // ---------------------------------------------------------------------------------------------------
 // ROWS (generate_ragged): every sequence sits at a position of its own, pos_dev[b] (device int32 [B]).  The grid is then
 // (blocks over one sequence's H * hd/2 pairs, B): blockIdx.y is the sequence, so the position is one scalar load per workgroup.
-template <typename T, bool ROWS = false>
+// VIA (ROWS only; DecodeSession(lookahead=k), mh_kv_append_rows_via): row b stores into cache sequence row_cache[b] of n_cache
+// instead of sequence b -- the rows of a group share their leader's -- and a row whose row_cache lies outside [0, n_cache) is
+// inactive: it returns before it touches qkv or a cache.  The two trailing arguments are read by VIA instantiations only.
+template <typename T, bool ROWS = false, bool VIA = false>
 __global__ __launch_bounds__(256) void kv_append_kernel(T* __restrict__ qkv, const float* __restrict__ cos_t,
                                                         const float* __restrict__ sin_t, T* __restrict__ kc,
                                                         T* __restrict__ vc, int64_t B, int H, int hd, int64_t Lmax,
-                                                        int64_t pos, const int32_t* __restrict__ pos_dev) {
+                                                        int64_t pos, const int32_t* __restrict__ pos_dev,
+                                                        const int32_t* __restrict__ row_cache = nullptr, int n_cache = 0) {
+  static_assert(!VIA || ROWS, "the row map goes with per-row positions");
   // one thread per (b, h, pair index i < hd/2): rotate q and k, store k and v rows
+  int64_t cseq = 0;  // (VIA) the cache sequence of this block's row
+  if constexpr (VIA) {
+    cseq = row_cache[blockIdx.y];
+    if (cseq < 0 || cseq >= n_cache) return;
+  }
   if constexpr (ROWS) {
     pos = pos_dev[blockIdx.y];
     if (pos < 0) return;
@@ -510,8 +520,9 @@ __global__ __launch_bounds__(256) void kv_append_kernel(T* __restrict__ qkv, con
     const T kr1 = from_f<T>(k1 * c - k2 * s), kr2 = from_f<T>(k2 * c + k1 * s);
     row[D + i] = kr1;
     row[D + i + half] = kr2;
-    T* kd = kc + ((b * H + h) * Lmax + pos) * hd;
-    T* vd = vc + ((b * H + h) * Lmax + pos) * hd;
+    const int64_t cb = VIA ? cseq : b;  // the cache sequence the row stores into
+    T* kd = kc + ((cb * H + h) * Lmax + pos) * hd;
+    T* vd = vc + ((cb * H + h) * Lmax + pos) * hd;
     kd[i] = kr1;
     kd[i + half] = kr2;
     vd[i] = row[2 * D + i];
@@ -548,6 +559,27 @@ extern "C" int mh_kv_append_rows(void* qkv, const float* cos_t, const float* sin
   const dim3 grid((unsigned)((H * (hd / 2) + 255) / 256), (unsigned)B);
   DISPATCH_T(dtype, (kv_append_kernel<T, true><<<grid, 256, 0, (hipStream_t)stream>>>((T*)qkv, cos_t, sin_t, (T*)kcache,
                                                                                       (T*)vcache, B, H, hd, Lmax, 0, row_pos)));
+  MH_LAUNCH_CHECK();
+  return MH_OK;
+}
+
+// the row map's own checks, behind MH_REQUIRE_ROWS (the two _via entry points share them)
+#define MH_REQUIRE_VIA(name)                                                                                           \
+  do {                                                                                                                 \
+    MH_REQUIRE(row_cache != nullptr, name ": row_cache is NULL (one device int32 cache sequence per row, -1: inactive)"); \
+    MH_REQUIRE(n_cache > 0 && n_cache < 65536, name ": bad args n_cache=%ld", (long)n_cache);                          \
+  } while (0)
+
+extern "C" int mh_kv_append_rows_via(void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache, int64_t B,
+                                     int H, int hd, int64_t Lmax, const int32_t* row_pos, const int32_t* row_cache,
+                                     int64_t n_cache, int dtype, void* stream) {
+  MH_REQUIRE_ROWS("kv_append_rows_via");
+  MH_REQUIRE_VIA("kv_append_rows_via");
+  MH_REQUIRE(qkv != nullptr && cos_t != nullptr && sin_t != nullptr && kcache != nullptr && vcache != nullptr,
+             "kv_append_rows_via: null buffer");
+  const dim3 grid((unsigned)((H * (hd / 2) + 255) / 256), (unsigned)B);
+  DISPATCH_T(dtype, (kv_append_kernel<T, true, true><<<grid, 256, 0, (hipStream_t)stream>>>(
+                        (T*)qkv, cos_t, sin_t, (T*)kcache, (T*)vcache, B, H, hd, Lmax, 0, row_pos, row_cache, (int)n_cache)));
   MH_LAUNCH_CHECK();
   return MH_OK;
 }
@@ -792,7 +824,10 @@ __device__ inline float group_sum(float v) {
 // ROWS with SHARED (APPEND only; DecodeSession(prefix_slots=G), mh_attn_prefix_partial_slots): the prompt a row shares is the one
 // in slot row_slot[b] of n_slots, pre_len_dev is slot_len [n_slots], and pre_b = min(slot_len[row_slot[b]], pre_max), or 0 for a
 // row whose row_slot lies outside [0, n_slots).  Such a row merges no partial: it does the arithmetic of the plain ROWS form.
-template <typename T, int HD, bool APPEND, bool SHARED = false, bool ROWS = false>
+// VIA (ROWS without APPEND or SHARED; DecodeSession(lookahead=k), mh_attn_decode_rows_via): row b attends to cache sequence
+// row_slot[b] of n_slots -- the argument pair carries the row map here -- instead of sequence b; a row whose entry lies outside
+// [0, n_slots) is inactive: it writes zeros to its o and returns.  Only the cache base address differs from the ROWS form.
+template <typename T, int HD, bool APPEND, bool SHARED = false, bool ROWS = false, bool VIA = false>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ qkv, T* kc, T* vc, T* __restrict__ o, int H,
                                                           int64_t Lmax, int64_t len, float scale,
                                                           const int32_t* __restrict__ pos_dev,
@@ -802,6 +837,7 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
                                                           int64_t n_bh = 0, const int32_t* __restrict__ row_slot = nullptr,
                                                           int n_slots = 0, int pre_max = 0) {
   static_assert(!SHARED || APPEND, "the shared-prefix form appends");
+  static_assert(!VIA || (ROWS && !APPEND && !SHARED), "the row map goes with the per-row form that reads a cache others appended to");
   // every kernel argument fetched at entry in one batch (hipcc sinks each s_load into the block that first uses it otherwise:
   // a scalar-cache miss + wait per block on a kernel whose whole run is a few microseconds)
   asm volatile("" ::"s"(qkv), "s"(kc), "s"(vc), "s"(o), "s"(H), "s"(Lmax), "s"(len), "s"(scale));
@@ -842,6 +878,15 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
   const int64_t b = ROWS ? (int64_t)blockIdx.y : bh / H;
   const int h = ROWS ? (int)blockIdx.x : (int)(bh - b * H);
   const int64_t D = (int64_t)H * HD;
+  int64_t cbh = bh;  // the (cache sequence, head) the block reads
+  if constexpr (VIA) {
+    const int cseq = row_slot[blockIdx.y];
+    if (cseq < 0 || cseq >= n_slots) {  // an inactive row: zeros, and no cache is touched
+      if (threadIdx.x < HD) o[b * D + (int64_t)h * HD + threadIdx.x] = from_f<T>(0.f);
+      return;
+    }
+    cbh = (int64_t)cseq * H + h;
+  }
   const int ch = lane % LPK, grp = lane / LPK;
   const T* qrow = qkv + b * 3 * D + (int64_t)h * HD;
   Pack<T> qv = ld16(qrow + ch * N);
@@ -884,8 +929,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const T* __restrict__ 
   float m = -INFINITY, l = 0.f, acc[N];
 #pragma unroll
   for (int e = 0; e < N; ++e) acc[e] = 0.f;
-  const T* kb = kc + bh * Lmax * HD;
-  const T* vb = vc + bh * Lmax * HD;
+  const T* kb = kc + cbh * Lmax * HD;
+  const T* vb = vc + cbh * Lmax * HD;
   // four steps of the key loop at a time with all K / V rows requested first: one step per memory round trip was one
   // round trip per 32 keys of head_dim 64 (13 us per layer at 128 cached events, r02 trace).  r03: the NEXT four steps are
   // requested before the current four are reduced (two register sets, 16 row loads per lane in flight): at batch 64 x 1024
@@ -1079,6 +1124,25 @@ extern "C" int mh_attn_decode_rows(const void* qkv, const void* kcache, const vo
   MH_REQUIRE_ROWS("attn_decode_rows");
   MH_REQUIRE(qkv != nullptr && kcache != nullptr && vcache != nullptr && o != nullptr, "attn_decode_rows: null buffer");
   return attn_decode_rows_launch(qkv, nullptr, nullptr, (void*)kcache, (void*)vcache, o, B, H, Lmax, scale, row_pos, dtype, stream);
+}
+
+// ... through the row map: row b reads cache sequence row_cache[b] (mh_kv_append_rows_via has stored the pair's new rows)
+extern "C" int mh_attn_decode_rows_via(const void* qkv, const void* kcache, const void* vcache, void* o, int64_t B, int H, int hd,
+                                       int64_t Lmax, float scale, const int32_t* row_pos, const int32_t* row_cache,
+                                       int64_t n_cache, int dtype, void* stream) {
+  MH_REQUIRE_ROWS("attn_decode_rows_via");
+  MH_REQUIRE_VIA("attn_decode_rows_via");
+  MH_REQUIRE(qkv != nullptr && kcache != nullptr && vcache != nullptr && o != nullptr, "attn_decode_rows_via: null buffer");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)H, (unsigned)B);
+#define LAUNCH_DEC_VIA(TT)                                                                                                   \
+  attn_decode_kernel<TT, 64, false, false, true, true><<<grid, 256, 0, st>>>(                                                \
+      (const TT*)qkv, (TT*)kcache, (TT*)vcache, (TT*)o, H, Lmax, 0, scale, row_pos, nullptr, nullptr, nullptr, 0, 1, 0, nullptr, 0, \
+      row_cache, (int)n_cache, 0)
+  if (dtype == MH_BF16) LAUNCH_DEC_VIA(bf16); else LAUNCH_DEC_VIA(float);
+#undef LAUNCH_DEC_VIA
+  MH_LAUNCH_CHECK();
+  return MH_OK;
 }
 
 extern "C" int mh_attn_decode_append_rows(const void* qkv, const float* cos_t, const float* sin_t, void* kcache, void* vcache,

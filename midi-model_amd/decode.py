@@ -112,6 +112,22 @@ to a pinned host block on the copy stream beside ``seq``, under the same one syn
 ``last_logp`` (np.float32 [B, T]; positions past an event's arity hold the pad token's value or, in the step-by-step form, what an
 earlier event left: the caller sums positions 0..arity).  Only the sampler call changes: admissions, forks and releases recapture
 nothing.  The key's form gains ``("logp",)`` at its end; ``logprobs=False`` is the session as it was: the same key, buffers and launches.
+
+``lookahead`` = k > 0 (seeded row_params sessions, bf16 cache, no prefix slots, no adapters; decode_pool(lookahead=k)): the
+B rows are B / (k + 1) GROUPS of k + 1 consecutive rows -- row 0 of a group its LEADER, rows 1..k its DRAFT rows -- and the K/V of a
+group live ONCE, in cache sequence g of ``kv1``, which is allocated for B / (k + 1) sequences (``kv2``, the token level, stays per
+row).  ``row_cache`` (device int32 [B], a fixed buffer the captured net graph reads; -1: the row is inactive) names the cache sequence
+of every row, and the net step's attention is the pair of ops_lookahead.py: every active row stores its K/V at ``pos[b]`` of its
+group's sequence, then every active row attends to rows [0, pos[b]] of it -- so a draft row at position p + j sees what the leader
+(at p) and the draft rows below it stored in the same layer.  ``set_inputs`` scatters the rows' inputs (``seq``), positions and
+``row_cache`` entries between the token steps and the net step, in one pinned block; the sampler's counter is ``pos[b]`` as in
+every seeded session, so draft row j samples the event of index p + j + 1 under its request's seed.  ``admit`` / ``fork`` /
+``hold`` / ``release`` then take GROUP indices where they take rows: a prompt's K/V goes into the group's cache sequence, the
+leader's hidden row, position and settings are written as a row's are, and the leader's settings (limit, temperature, top-p, top-k,
+both masks, seed) are copied into the group's draft rows, which start inactive.  Stale K/V of rejected drafts lie at or above the
+leader's next position, and the next net step overwrites the rows it reads before it reads them.  Nothing is recaptured per step,
+admission, fork or release.  The key's form gains ``("lookahead", k)``; ``lookahead=0`` is the session as it was: the same key,
+buffers and launches.
 """
 from __future__ import annotations
 
@@ -146,7 +162,7 @@ class DecodeSession:
     def __init__(self, model, B: int, capacity: int, temp: float, top_p: float, top_k: int, shared_capacity: int = 0,
                  ragged: bool = False, row_params: bool = False, seeded: bool = False, prefix_slots: int = 0,
                  prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False, lora_slots: int = 0,
-                 lora_rank: int = 64):
+                 lora_rank: int = 64, lookahead: int = 0):
         tok = model.tokenizer
         self.model, self.B, self.cap, self.temp = model, B, capacity, float(temp)
         self.top_p, self.top_k = float(top_p), int(top_k)
@@ -158,7 +174,13 @@ class DecodeSession:
         self.kv_dtype = kv_dtype
         self.logprobs = bool(logprobs)
         self.lora_slots, self.lora_rank = int(lora_slots), int(lora_rank)
-        if lora_slots:  # (the call without the option is the call it was)
+        self.lookahead = int(lookahead) if lookahead else 0
+        self.gw = self.lookahead + 1          # rows per group (1: every row is its own group, the session as it was)
+        self.groups = B // self.gw            # ... and the sequences of the event-level cache
+        if lookahead:  # (the call without the option is the call it was)
+            self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params, seeded,
+                                     prefix_slots, prefix_capacity, kv_dtype, logprobs, lora_slots, lora_rank, lookahead)
+        elif lora_slots:
             self.key = self.make_key(model, B, capacity, temp, top_p, top_k, shared_capacity, ragged, row_params, seeded,
                                      prefix_slots, prefix_capacity, kv_dtype, logprobs, lora_slots, lora_rank)
         else:
@@ -169,8 +191,8 @@ class DecodeSession:
         spec, tspec = model._specs["net"], model._specs["net_token"]
         if kv_dtype == "fp8":  # codes and a scale pair per (row, head, event); never grown
             self.kv1 = KVStateQ(spec, B, capacity, model._flat)
-        else:
-            self.kv1 = KVState(spec, B, capacity, model._flat)  # (shared: the generated suffix only)
+        else:  # (lookahead: a sequence per GROUP)
+            self.kv1 = KVState(spec, self.groups, capacity, model._flat)  # (shared: the generated suffix only)
         self.kv2 = KVState(tspec, B, self.T, model._flat)
         self.kvp = self.pre_len = self.ws = None
         if self.shared_capacity > 0:
@@ -178,6 +200,9 @@ class DecodeSession:
             self.kvp = KVState(spec, 1, self.shared_capacity, model._flat)  # the prompt, once
             self.pre_len = torch.zeros(1, dtype=torch.int32, device=dev)      # its length (device side, beside pos)
             self.ws = torch.empty(shared.workspace_floats(B, spec.H, self.shared_capacity), dtype=torch.float32, device=dev)
+        # (lookahead) the cache sequence of every row, -1: inactive; read by the captured net graph
+        self.row_cache = torch.full((B,), -1, dtype=torch.int32, device=dev) if self.lookahead else None
+        self._look_stage = None    # the pinned host block of the last set_inputs
         self.kvs = self.slot_len = self.row_slot = None
         if self.prefix_slots > 0:
             from .ops_share import workspace_floats
@@ -275,7 +300,18 @@ class DecodeSession:
 
     @staticmethod
     def make_key(model, B, capacity, temp, top_p, top_k, shared_capacity=0, ragged=False, row_params=False, seeded=False,
-                 prefix_slots=0, prefix_capacity=0, kv_dtype=None, logprobs=False, lora_slots=0, lora_rank=64):
+                 prefix_slots=0, prefix_capacity=0, kv_dtype=None, logprobs=False, lora_slots=0, lora_rank=64, lookahead=0):
+        if lookahead:
+            if isinstance(lookahead, bool) or not isinstance(lookahead, (int, np.integer)) or lookahead < 1:
+                raise ValueError(f"DecodeSession: lookahead={lookahead!r} -- an integer >= 1 (draft rows per group), or 0 for none")
+            if not (ragged and row_params and seeded):
+                raise ValueError("DecodeSession: lookahead is a form of the per-row seeded session -- it needs ragged=True, "
+                                 "row_params=True, seeded=True (exact verification rests on the seeded sampler's counter)")
+            if prefix_slots or prefix_capacity or kv_dtype is not None or lora_slots or shared_capacity:
+                raise ValueError("DecodeSession: lookahead is not available together with prefix slots, kv_dtype or lora_slots")
+            if B % (int(lookahead) + 1) or B > 256:
+                raise ValueError(f"DecodeSession: lookahead={lookahead} needs whole groups of {int(lookahead) + 1} rows and at most "
+                                 f"256 rows in all: {B} rows")
         if lora_slots:
             if not (ragged and row_params):
                 raise ValueError("DecodeSession: lora_slots is a form of the per-row session -- it needs ragged=True, row_params=True")
@@ -324,6 +360,8 @@ class DecodeSession:
                 form += (("logp",),)
             if lora_slots:  # (likewise)
                 form += (("lora", int(lora_slots), int(lora_rank)),)
+            if lookahead:  # (likewise)
+                form += (("lookahead", int(lookahead)),)
             return (model._flat.data_ptr(), model._flat.dtype, B, capacity, form)
         key = (model._flat.data_ptr(), model._flat.dtype, B, capacity, float(temp), float(top_p), int(top_k))
         if ragged:
@@ -358,7 +396,10 @@ class DecodeSession:
             if self.kvs is not None:  # ... and behind the prompt of its slot, if it names one
                 from .ops_share import SlotPrefix
                 sh = SlotPrefix(self.kvs, self.slot_len, self.row_slot, self.ws)
-            if self.lora1 is not None:
+            if self.row_cache is not None:  # the rows of a group on their leader's cache sequence
+                engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, folded=self.fold1, out=self.hidden, row_pos=self.pos,
+                                    wide=self.wide, row_cache=self.row_cache)
+            elif self.lora1 is not None:
                 engine.stack_decode(spec, m._W["net"], e, self.rope1, self.kv1, folded=self.fold1, out=self.hidden, row_pos=self.pos,
                                     wide=self.wide, shared=sh, lora=self.lora1)
             else:
@@ -528,6 +569,8 @@ class DecodeSession:
             self.slot_len.zero_()
             self.row_slot.fill_(-1)
             self._reset_slots_host()
+        if self.row_cache is not None:  # every row inactive
+            self.row_cache.fill_(-1)
         if self.row_adapter is not None:  # no row names an adapter and every slot is empty: nothing outlives the session's user
             self.row_adapter.fill_(-1)
             for g in list(self._lora_loaded):
@@ -595,8 +638,8 @@ class DecodeSession:
         """tokens [B, S, T]: causal forward over the prompt from an empty cache; leaves hidden = last position.
         A shared session runs ROW 0 alone (the caller has checked that the rows are equal) into ``kvp`` and hands its last hidden
         row to all B rows; the suffix cache starts empty."""
-        if self.kv_dtype is not None:
-            raise ValueError("DecodeSession.prefill: an fp8-cache session is filled by admit() alone")
+        if self.kv_dtype is not None or self.lookahead:
+            raise ValueError("DecodeSession.prefill: an fp8-cache or lookahead session is filled by admit() alone")
         m = self.model
         spec = m._specs["net"]
         B, S, T = tokens.shape
@@ -672,8 +715,8 @@ class DecodeSession:
         """tokens [M, T]: the B prompts laid end to end, prompt b of lengths[b] events.  One packed causal forward from empty
         caches (engine.stack_prefill_seqs); leaves hidden[b] = prompt b's last position and pos[b] = lengths[b].  Prompts of one
         length take prefill()'s uniform forward instead, so that generate_ragged continues them exactly as generate() does."""
-        if self.kv_dtype is not None:
-            raise ValueError("DecodeSession.prefill_ragged: an fp8-cache session is filled by admit() alone")
+        if self.kv_dtype is not None or self.lookahead:
+            raise ValueError("DecodeSession.prefill_ragged: an fp8-cache or lookahead session is filled by admit() alone")
         m = self.model
         spec = m._specs["net"]
         lengths = [int(n) for n in lengths]
@@ -724,6 +767,9 @@ class DecodeSession:
         None) travels in the same block, and the prompts are prefilled against that adapter's MERGED event-level weights
         (``_merged_weights``; the unfolded forward) -- so the prompt's K/V come from W + s B A in bf16, which is how the reference
         serves an adapter, and the decoded events from the unmerged form.
+        A lookahead session: ``rows`` are GROUP indices -- prompt s's K/V goes into cache sequence rows[s], the LEADER row
+        rows[s] (k + 1) takes hidden, position and the settings, ``row_cache`` names the sequence for it, and the group's draft rows
+        take a copy of the leader's settings and start inactive (``_spread_group``).
         Everything is checked on the host first; ``ValueError`` before any launch."""
         if not (self.ragged and self.row_params):
             raise ValueError("DecodeSession.admit: rows are admitted into a ragged=True, row_params=True session only")
@@ -732,7 +778,8 @@ class DecodeSession:
         spec = m._specs["net"]
         lengths, limits = [int(n) for n in lengths], [int(n) for n in limits]
         n, V = len(lengths), self.V
-        ids = check_rows(rows, n, self.B)
+        ids = check_rows(rows, n, self.groups)   # (cache sequences: the rows themselves unless the session has groups)
+        lead = [g * self.gw for g in ids] if self.lookahead else ids   # ... and the rows that take the state
         vals = [list(np.asarray(x).reshape(-1).tolist()) for x in (temp, top_p, top_k)]
         first_masks, bans = torch.as_tensor(first_masks), torch.as_tensor(bans)
         M, T = tokens.shape
@@ -769,7 +816,7 @@ class DecodeSession:
             raise ValueError(f"admit: rows {[r for r in ids if self.row_slot_host[r] >= 0]} still name a prefix slot: release them first")
         # ---- the one host block: [idx i64 | last i64 | rows i32 | lengths i32 | limits i32 | top_k i32 | temp f32 | top_p f32 |
         #      first u8 | ban u8 (| seeds i64)], every section on a multiple of 16 bytes
-        sections = [(np.int64, ids), (np.int64, np.cumsum(lengths) - 1), (np.int32, ids), (np.int32, lengths), (np.int32, limits),
+        sections = [(np.int64, lead), (np.int64, np.cumsum(lengths) - 1), (np.int32, ids), (np.int32, lengths), (np.int32, limits),
                     (np.int32, vals[2]), (np.float32, vals[0]), (np.float32, vals[1]),
                     (np.uint8, first_masks.numpy().reshape(-1)), (np.uint8, bans.numpy().reshape(-1))]
         if self.seeded:
@@ -812,6 +859,52 @@ class DecodeSession:
                 self.row_slot_host[r], self.slot_len_host[g], self.slot_refs[g] = g, L, 1
         elif self.kvs is not None:
             self.row_slot.index_fill_(0, idx, -1)
+        if self.lookahead:
+            self.row_cache.index_copy_(0, idx, rows_dev)
+            self._spread_group(ids)
+
+    def _spread_group(self, groups) -> None:
+        """(lookahead) the draft rows of ``groups`` <- their leader's limit, temperature, top-p, top-k, masks and seed; inactive
+        (``row_cache`` = -1) at position 0.  Device-side row copies behind the scatter that wrote the leaders."""
+        k, gw = self.lookahead, self.gw
+        dev = self.model.device
+        drafts = torch.tensor([g * gw + j for g in groups for j in range(1, gw)], dtype=torch.int64).to(dev)
+        leads = torch.tensor([g * gw for g in groups for _ in range(k)], dtype=torch.int64).to(dev)
+        for buf in (self.pos_limit, self.temp_rows, self.top_p_rows, self.top_k_rows, self.first_mask, self.ban, self.seed_rows):
+            buf.index_copy_(0, drafts, buf.index_select(0, leads))
+        self.pos.index_fill_(0, drafts, 0)
+        self.row_cache.index_fill_(0, drafts, -1)
+
+    def set_inputs(self, rows, events, positions, caches) -> None:
+        """(lookahead) between the token steps and the net step: ``seq[rows]`` = events (int64 [n, T]: the event each row consumes),
+        ``pos[rows]`` = positions and ``row_cache[rows]`` = caches (the row's group, or -1 for a row that sits the step out), in ONE
+        pinned host block (``_stage_block``) and three index_copy_ calls.  The caller keeps two rows of one group off one position
+        and every position inside the capacity (checked here on the host; ``ValueError`` before any copy)."""
+        if not self.lookahead:
+            raise ValueError("DecodeSession.set_inputs: not a lookahead session")
+        from .ops_pool import check_rows
+        ids = check_rows(rows, len(rows), self.B)
+        n = len(ids)
+        events = np.asarray(events, dtype=np.int64).reshape(n, self.T) if n else np.zeros((0, self.T), dtype=np.int64)
+        positions, caches = [int(p) for p in positions], [int(c) for c in caches]
+        if len(positions) != n or len(caches) != n:
+            raise ValueError(f"set_inputs: {n} rows, {len(positions)} positions, {len(caches)} cache sequences")
+        if not n:
+            return
+        for r, p, c in zip(ids, positions, caches):
+            if c != -1 and (c != r // self.gw or not 0 <= p < self.cap):
+                raise ValueError(f"set_inputs: row {r} at position {p} of cache sequence {c}: an active row belongs to its own group "
+                                 f"({r // self.gw}) and stands inside the capacity {self.cap}")
+        taken = [(c, p) for p, c in zip(positions, caches) if c != -1]
+        if len(set(taken)) != len(taken):
+            raise ValueError(f"set_inputs: two rows of one group at one position: {sorted(taken)}")
+        if events.min() < 0 or events.max() >= self.V:
+            raise ValueError(f"set_inputs: a token id outside [0, {self.V})")
+        idx, ev_dev, pos_dev, cache_dev = self._stage_block(
+            [(np.int64, ids), (np.int64, events.reshape(-1)), (np.int32, positions), (np.int32, caches)], "_look_stage")
+        self.seq.index_copy_(0, idx, ev_dev.view(n, self.T))
+        self.pos.index_copy_(0, idx, pos_dev)
+        self.row_cache.index_copy_(0, idx, cache_dev)
 
     _STAGE_TYPES = {np.int64: torch.int64, np.int32: torch.int32, np.float32: torch.float32, np.uint8: torch.uint8}
 
@@ -855,8 +948,9 @@ class DecodeSession:
         from .ops_fork import check_pairs
         V = self.V
         limits = [int(n) for n in limits]
-        src, dst, lengths = check_pairs(src_rows, dst_rows, lengths, self.B, self.cap)
+        src, dst, lengths = check_pairs(src_rows, dst_rows, lengths, self.groups, self.cap)   # (lookahead: GROUP indices)
         n = len(src)
+        gw = self.gw   # the rows that give and take the state: the groups' leaders (gw == 1: the rows themselves)
         vals = [list(np.asarray(x).reshape(-1).tolist()) for x in (temp, top_p, top_k)]
         first_masks, bans = torch.as_tensor(first_masks), torch.as_tensor(bans)
         if len(limits) != n or any(len(v) != n for v in vals):
@@ -901,7 +995,8 @@ class DecodeSession:
                     copies = [(s, d, L - p) for s, d, L, p in zip(src, dst, lengths, pre) if L - p > 0]
         # ---- the one host block: [dst i64 | src i64 | src, dst, lengths i32 [3, n] | limits i32 | top_k i32 | temp f32 | top_p f32 |
         #      first u8 | ban u8 | held u8 (| seeds i64)]
-        sections = [(np.int64, dst), (np.int64, src), (np.int32, src + dst + lengths), (np.int32, limits), (np.int32, vals[2]),
+        sections = [(np.int64, [d * gw for d in dst]), (np.int64, [s * gw for s in src]), (np.int32, src + dst + lengths),
+                    (np.int32, limits), (np.int32, vals[2]),
                     (np.float32, vals[0]), (np.float32, vals[1]), (np.uint8, first_masks.numpy().reshape(-1)),
                     (np.uint8, bans.numpy().reshape(-1)), (np.uint8, held)]
         if self.seeded:
@@ -940,6 +1035,10 @@ class DecodeSession:
             self.row_adapter.index_copy_(0, idx, self.row_adapter.index_select(0, from_idx))
         if self.kvs is not None:
             self.row_slot.index_copy_(0, idx, more_dev[1 if self.seeded else 0])
+        if self.lookahead:  # the destination groups: the leader on its own cache sequence, the draft rows inactive on its settings
+            self.row_cache.index_copy_(0, idx, pairs[1])
+            self._spread_group(dst)
+        if self.kvs is not None:
             for d, g in zip(dst, src_slot):
                 self.row_slot_host[d] = g
                 if g >= 0:
@@ -953,7 +1052,7 @@ class DecodeSession:
         if not (self.ragged and self.row_params):
             raise ValueError("DecodeSession.hold: rows are held on a ragged=True, row_params=True session only")
         from .ops_pool import check_rows
-        ids = check_rows(rows, len(rows), self.B)
+        ids = [g * self.gw for g in check_rows(rows, len(rows), self.groups)]   # (lookahead: groups -> their leaders)
         if not ids:
             return
         if self.held_hidden is None:
@@ -970,12 +1069,16 @@ class DecodeSession:
         if not (self.ragged and self.row_params):
             raise ValueError("DecodeSession.release: rows are released on a ragged=True, row_params=True session only")
         from .ops_pool import check_rows
-        ids = check_rows(rows, len(rows), self.B)
+        ids = check_rows(rows, len(rows), self.groups)
         if not ids:
             return
+        if self.lookahead:  # groups: every row of them, and all of them inactive
+            ids = [g * self.gw + j for g in ids for j in range(self.gw)]
         idx = torch.tensor(ids, dtype=torch.int64).to(self.model.device)
         self.pos.index_fill_(0, idx, 0)
         self.pos_limit.index_fill_(0, idx, 0)
+        if self.row_cache is not None:
+            self.row_cache.index_fill_(0, idx, -1)
         if self.row_adapter is not None:
             self.row_adapter.index_fill_(0, idx, -1)
         if self.kvs is not None:

@@ -831,7 +831,7 @@ class LoraStack:
 
 def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTable, kv: KVState, pos_dev=None,
                  folded=None, final_norm: bool = True, x_ids=None, out: Optional[torch.Tensor] = None, shared=None,
-                 row_pos=None, wide: Optional[bool] = None, lora: Optional[LoraStack] = None):
+                 row_pos=None, wide: Optional[bool] = None, lora: Optional[LoraStack] = None, row_cache=None):
     """x [B, D]: one new position per sequence at index kv.len (q_len == 1 => no causal mask,
     TF:integrations/sdpa_attention.py:120).
 
@@ -866,12 +866,21 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
     ``lora`` (a LoraStack whose ``refresh`` followed the last load): an adapter per row, unmerged -- the fused folded form only
     (bf16, at most 256 rows, ``folded`` given), ``ValueError`` before any launch otherwise.  Each of the layer's four projections is
     preceded by its shrink (mh_lora_shrink_rows) and takes the expand as a second operand pair (mh_gemm_skinny_ext): 9 launches per
-    layer.  The attention step, whichever form it has, is untouched."""
+    layer.  The attention step, whichever form it has, is untouched.
+    ``row_cache`` (device int32 [B], with ``row_pos``; DecodeSession(lookahead=k)): row b belongs to cache sequence row_cache[b] of
+    ``kv`` -- a cache of kv.B <= B sequences that the rows of a group share -- or to none (-1: the row is inactive, stores nothing and
+    attends to nothing).  The attention step of every form of the layer is the pair mh_kv_append_rows_via +
+    mh_attn_decode_rows_via (ops_lookahead.py): the append completes first, so a row sees the keys the rows of its group stored
+    below its position in the same layer; 6 launches per folded layer instead of 5.  Without ``row_pos``, with ``shared``, ``lora``
+    or a ``KVStateQ``: ``ValueError`` before any launch."""
     _check_heads(spec)
     B, D = (x_ids.shape[0], x.shape[1]) if x_ids is not None else x.shape
     assert x_ids is None or folded is not None
     H, I, hd = spec.H, spec.I, spec.hd
     quant = isinstance(kv, KVStateQ)
+    if row_cache is not None and (row_pos is None or shared is not None or lora is not None or quant or pos_dev is not None):
+        raise ValueError("stack_decode(row_cache=...): the row map goes with per-row positions (row_pos) on the plain cache alone -- "
+                         "not with pos_dev, a shared prompt, prefix slots, LoRA adapters or the fp8 cache")
     if quant and (row_pos is None or shared is not None):
         _refuse_kvq(kv, "stack_decode without row_pos" if row_pos is None else "stack_decode(shared=...)")
     from .ops_share import SlotPrefix
@@ -884,6 +893,10 @@ def stack_decode(spec: StackSpec, W: StackTensors, x: torch.Tensor, rope: RopeTa
         def attend(qkv, o, li):
             ops.attn_decode_append_rows_fp8(qkv, rope.cos, rope.sin, kv.k8[li], kv.v8[li], kv.sc[li], o, B, H, hd, kv.cap, spec.scale,
                                             row_pos)
+    elif row_cache is not None:
+        def attend(qkv, o, li):
+            ops.kv_append_rows_via(qkv, rope.cos, rope.sin, kv.k[li], kv.v[li], B, H, hd, kv.cap, row_pos, row_cache)
+            ops.attn_decode_rows_via(qkv, kv.k[li], kv.v[li], o, B, H, hd, kv.cap, spec.scale, row_pos, row_cache)
     elif row_pos is not None:
         def attend(qkv, o, li):
             if fused:

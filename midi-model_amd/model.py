@@ -867,7 +867,7 @@ class MIDIModel(nn.Module):
 
     def decode_pool(self, rows: int, capacity: int, generator=None, seeded: bool = False, prefix_slots: int = 0,
                     prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False, lora_slots: int = 0,
-                    lora_rank: int = 64):
+                    lora_rank: int = 64, lookahead: Optional[int] = None):
         """(ours) a ``pool.DecodePool`` on this model: ``rows`` decode rows that requests are admitted into and released from
         while the batch runs (continuous batching).  ``capacity``: cache rows per decode row; a request needs
         max_len + 1 <= capacity (the session's own capacity is rounded up as every session's is, 256 x 2^k).  The pool takes one
@@ -884,8 +884,15 @@ class MIDIModel(nn.Module):
         ``lora_slots`` = G > 0 with ``lora_rank`` = R: the pool keeps G LoRA adapters of rank at most R beside the base weights
         (``pool.load_adapter``) and ``submit(..., adapter=id)`` decodes a request under one of them, unmerged, in the same batch as
         requests on other adapters and on none (pool.py "LORA ADAPTERS"); a bf16 model, at most 256 rows, G R a
-        multiple of 256 (``ValueError``); with any of the options above.  Nothing is launched here."""
+        multiple of 256 (``ValueError``); with any of the options above.
+        ``lookahead`` = k >= 1 (``seeded=True`` only; with ``logprobs``, not with prefix slots, ``kv_dtype`` or ``lora_slots``; rows x
+        (k + 1) <= 256; ``ValueError`` otherwise): every request owns k + 1 session rows, k of which verify guessed next events
+        (``pool.proposer``), so a request whose guesses are right finishes in fewer steps and its ids never depend on the guesses
+        (pool.py "LOOKAHEAD").  Nothing is launched here."""
         from .pool import DecodePool
+        if lookahead is not None:
+            return DecodePool(self, rows, capacity, generator, seeded, prefix_slots, prefix_capacity, kv_dtype=kv_dtype,
+                              logprobs=logprobs, lora_slots=lora_slots, lora_rank=lora_rank, lookahead=lookahead)
         if lora_slots:
             return DecodePool(self, rows, capacity, generator, seeded, prefix_slots, prefix_capacity, kv_dtype=kv_dtype,
                               logprobs=logprobs, lora_slots=lora_slots, lora_rank=lora_rank)
@@ -900,7 +907,7 @@ class MIDIModel(nn.Module):
 
     def generate_pool(self, requests, rows: int, capacity: Optional[int] = None, generator=None,
                       kv_dtype: Optional[str] = None, logprobs: bool = False, adapters: Optional[dict] = None,
-                      lora_rank: int = 64) -> list:
+                      lora_rank: int = 64, lookahead: Optional[int] = None) -> list:
         """(ours) ``requests``: a list of dicts, each the keyword arguments of ``DecodePool.submit`` (``prompt`` and any of max_len,
         temp, top_p, top_k, ban_eos, disable_patch_change, disable_control_change, disable_channels, seed).  If EVERY request
         carries ``"seed"`` the pool is a seeded one; some with and some without is a ``ValueError``.  They are submitted in order
@@ -910,7 +917,8 @@ class MIDIModel(nn.Module):
         ``logprobs=True``: -> a list of ``(events, logprobs)`` pairs instead, ``logprobs`` the request's ``DecodePool.logprobs``
         array (np.float32, one value per generated event, aligned with ``events[len(prompt):]``).
         ``adapters`` = {name: src} (``src`` as ``DecodePool.load_adapter`` takes it): the pool gets a slot for each (as many of rank
-        ``lora_rank`` as make slots x rank a multiple of 256) and a request's ``"adapter": name`` decodes it under that adapter."""
+        ``lora_rank`` as make slots x rank a multiple of 256) and a request's ``"adapter": name`` decodes it under that adapter.
+        ``lookahead``: as ``decode_pool`` takes it (every request then carries a seed); the pool's built-in proposer guesses."""
         requests = list(requests)
         if not requests:
             return []
@@ -927,6 +935,8 @@ class MIDIModel(nn.Module):
             kvq.update(lora_slots=-(-len(adapters) // per) * per, lora_rank=lora_rank)
         elif any(r.get("adapter") is not None for r in requests):
             raise ValueError("generate_pool: a request names an adapter and ``adapters`` is empty")
+        if lookahead is not None:
+            kvq["lookahead"] = lookahead
         with self.decode_pool(rows, capacity, generator, seeded=with_seed > 0, **kvq) as pool:
             if adapters:
                 names = {name: pool.load_adapter(src) for name, src in adapters.items()}
@@ -987,8 +997,10 @@ class MIDIModel(nn.Module):
     def _checkout_session(self, B: int, need: int, temp: float, top_p: float, top_k: int, shared_need: int = 0,
                           ragged: bool = False, row_params: bool = False, seeded: bool = False, prefix_slots: int = 0,
                           prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False, lora_slots: int = 0,
-                          lora_rank: int = 64):
-        """``lora_slots`` / ``lora_rank`` (row_params only): the session with that many LoRA adapter slots (DecodeSession); a pooled
+                          lora_rank: int = 64, lookahead: int = 0):
+        """``lookahead`` = k (seeded row_params only): the session of B rows in groups of k + 1 that share a cache sequence
+        (DecodeSession); a pooled session of its own kind, 0: the session as it was.
+        ``lora_slots`` / ``lora_rank`` (row_params only): the session with that many LoRA adapter slots (DecodeSession); a pooled
         session of its own kind, 0: the session as it was.
         ``logprobs`` (row_params only): the session whose samplers also write the drawn ids' log-probabilities (DecodeSession); a
         pooled session of its own kind, False: the session as it was.
@@ -1016,7 +1028,10 @@ class MIDIModel(nn.Module):
             pcap = 256
             while pcap < prefix_capacity:
                 pcap *= 2
-        if lora_slots:
+        if lookahead:
+            key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap,
+                                         kv_dtype, logprobs, lora_slots, lora_rank, lookahead=lookahead)
+        elif lora_slots:
             key = DecodeSession.make_key(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap,
                                          kv_dtype, logprobs, lora_slots, lora_rank)
         elif logprobs:
@@ -1041,6 +1056,9 @@ class MIDIModel(nn.Module):
         if found is not None:
             found.refresh()  # weights may have been trained / merged since the session derived its folded copies
             return found
+        if lookahead:
+            return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap, kv_dtype,
+                                 logprobs=logprobs, lora_slots=lora_slots, lora_rank=lora_rank, lookahead=lookahead)
         if lora_slots:
             return DecodeSession(self, B, cap, temp, top_p, top_k, scap, ragged, row_params, seeded, prefix_slots, pcap, kv_dtype,
                                  logprobs=logprobs, lora_slots=lora_slots, lora_rank=lora_rank)

@@ -623,9 +623,14 @@ _KVQ = ("kv_store_seqs_rows_fp8", "attn_decode_append_rows_fp8", "kv_fork_rows_f
 _LOGP = ("sample_top_p_k_rows_logp", "sample_top_p_k_seeded_logp")
 # ... and the projections of a decode batch with a LoRA adapter per row (ops_lora.py)
 _LORA = ("lora_shrink_rows", "gemm_skinny_ext", "skinny_ext_ok")
+# ... and the per-row K/V append and decode attention through a row map (ops_lookahead.py; stand-ins in tests/emu_lookahead.py)
+_LOOKAHEAD = ("kv_append_rows_via", "attn_decode_rows_via")
 
 
 def __getattr__(name: str):
+    if name in _LOOKAHEAD:
+        from . import ops_lookahead
+        return getattr(ops_lookahead, name)
     if name in _LORA:
         from . import ops_lora
         return getattr(ops_lora, name)

@@ -141,6 +141,43 @@ batch and one copy of the weights.  The stated limits:
   * a bf16 model, at most 256 rows, ``G R`` a multiple of 256 (``ValueError`` at construction otherwise).
 A pool made without ``lora_slots`` takes the session, the graphs and the launches it took.
 
+LOOKAHEAD.  ``model.decode_pool(rows=R, capacity=C, seeded=True, lookahead=k)`` makes one request finish in FEWER steps: a
+step costs its launches whether it carries 1 row or 64, so each of the R requests owns a GROUP of k + 1 consecutive session rows (the
+session has R (k + 1) <= 256), row 0 its LEADER, rows 1..k carrying DRAFTS -- guessed events for the next k positions -- and every
+``step()`` verifies the guesses of the step before.  The seeded sampler's variate is a function of (request seed, index of the event,
+token position, rank), not of the row or the step, so what draft row j samples for index t + j behind a guessed prefix IS the event
+the request would have sampled there if the prefix was right.  One ``step()``:
+  1. ``sample_event`` over all rows: row j of a group samples s_j for event index t + j;
+  2. acceptance, on the host (``DecodePool.accept``): s_0 is true; m is the largest number such that for every 1 <= i <= m the draft
+     row i consumed in the previous net step equals s_(i-1) in all 8 tokens; s_0 .. s_m are reported, in order -- one request id
+     may appear several times in a step's list -- and an EOS or ``max_len`` inside the run ends the request there;
+  3. ``pool.proposer(history, k)`` -> up to k drafts for the next indices, ``np.ndarray [<= k, 8]``; the built-in one
+     (``propose_ngram``) finds the most recent earlier occurrence of the last n events of prompt + result (n = 3, then 2; exact
+     8-token equality) and proposes what followed it.  It is an attribute: assign any callable.  Drafts that could only sample
+     events at or past ``max_len`` are cut off; rows without a draft sit the step out (no K/V written, nothing read);
+  4. one pinned-block scatter (``DecodeSession.set_inputs``: seq[leader] = s_m, seq[leader + j] = draft j, their positions and
+     cache entries), then the net step.  Lookahead pools never queue the net step ahead of the host's decision.
+The K/V of a group live once, in its leader's cache sequence (``kv1`` holds R sequences, not R (k + 1)); attention is the pair
+``mh_kv_append_rows_via`` + ``mh_attn_decode_rows_via``, 6 launches per layer instead of 5.  ``submit(n=)``, ``fork``, ``hold``,
+``held``, ``drop`` and ``logprobs`` work, in units of groups; an accepted event's log-likelihood is read from the row that sampled it.
+THE PROMISE: a request's ids and log-likelihoods do NOT depend on what the drafts were -- all right, all wrong, none, or anything
+between gives the same ids -- at equal launch shapes (the same session row count), the seeded pool's own limit.  The stated limits:
+  * equality with a pool made WITHOUT ``lookahead`` is NOT promised: the attention pair may order its additions differently from
+    the fused ``mh_attn_decode_append_rows``, and the session row count differs;
+  * ``ValueError`` at construction, before any launch: ``lookahead`` without ``seeded=True``; together with ``prefix_slots``,
+    ``kv_dtype`` or ``lora_slots``; R (k + 1) > 256; k < 1;
+  * a proposer must be a pure guess: whatever it returns changes the number of steps, never the result; one that returns anything
+    but ``[<= k, 8]`` token ids inside the vocabulary is a ``ValueError`` in ``step()``, before the scatter;
+  * what it buys on a real checkpoint is unmeasured here (no pretrained weights in the repository): DESIGN 7.14 has the mechanism's
+    overhead and its ceiling, and where it loses.
+Measured (one MI355X, ``profiles/pool_lookahead_ab.txt``; ``tools/bench_pool_lookahead.py``, tv2o-medium bf16, 64 prompt
+events, 128 generated, median steps): one request, k = 3: a step of 1.17 ms against the plain pool's 0.99 (no drafts: the overhead,
+861 against 1002 events/s) and 3390 events/s with every guess right (3.4 x; 3.97 events a step); k = 7: 1.19 ms, 6654 events/s (6.5
+x); eight requests: steps 1.33 x and 1.37 x the plain pool's, ceilings 2.8 x and 5.2 x.  A plain pool of the same R (k + 1) rows
+beats even the ceiling once 80 to 90 % of its rows hold requests: the option is for mostly empty pools.  The built-in proposer on
+the trained toy model of the parity tests guessed 6 times in 2040 events and was never right (it lost 7 %): a toy, not a checkpoint.
+A pool made without ``lookahead`` takes the session, the key, the graphs and the launches it took.
+
 Out of scope:
   * a background thread or server loop -- the caller owns the loop (and the thread: one pool, one thread);
   * shrinking the row caches of a pool with prefix slots, or a prompt shared ACROSS pools;
@@ -171,12 +208,33 @@ import torch
 _SETTINGS = ("max_len", "temp", "top_p", "top_k", "ban_eos", "disable_patch_change", "disable_control_change", "disable_channels")
 
 
+def propose_ngram(history: np.ndarray, k: int) -> np.ndarray:
+    """the built-in proposer of a lookahead pool: ``history`` [N, 8] (prompt + result so far) -> up to k guessed next events, [<= k,
+    8] int64.  The most recent EARLIER occurrence of the last n events (exact 8-token equality), n = 3 then 2; the guess is what
+    followed it, as far as the history goes.  No occurrence, or a history of at most n events: no guess."""
+    history = np.asarray(history)
+    N = len(history)
+    for n in (3, 2):
+        if N <= n:
+            continue
+        ok = np.ones(N - n, dtype=bool)   # ok[i]: history[i : i + n] equals the last n events (i < N - n: an earlier occurrence)
+        for j in range(n):
+            ok &= (history[j:N - n + j] == history[N - n + j]).all(axis=1)
+        hits = np.nonzero(ok)[0]
+        if hits.size:
+            at = int(hits[-1]) + n
+            return history[at:at + k].astype(np.int64, copy=True)
+    return np.zeros((0, history.shape[1] if history.ndim == 2 else 8), dtype=np.int64)
+
+
 class _Request:
     # (rp["seed"]: a seeded pool's request; prompt: a child's holds its parent's result at the fork; group: the size of the sibling
     #  group this request LEADS in the queue, 0 for the siblings behind it; kw: the settings as given, a child's defaults)
     #  share: the request continues a prompt that sits in a prefix slot -- a share_prefix submit, its siblings, their fork children)
     #  logp: ll of every event the request generated itself, beside ``events`` (a pool with logprobs=True; empty otherwise)
-    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done", "hold", "held", "eos", "group", "kw", "share", "logp", "adapter")
+    #  drafts: (a lookahead pool) the guessed events the request's draft rows consumed in the last net step, [<= k, 8]
+    __slots__ = ("prompt", "max_len", "rp", "events", "row", "done", "hold", "held", "eos", "group", "kw", "share", "logp", "adapter",
+                 "drafts")
 
     def __init__(self, prompt: np.ndarray, rp: dict, kw: dict, hold: bool = False, group: int = 1, share: bool = False):
         self.prompt, self.rp, self.max_len, self.kw, self.share = prompt, rp, rp["max_len"][0], kw, bool(share)
@@ -186,6 +244,7 @@ class _Request:
         self.done = False
         self.hold, self.held, self.eos, self.group = bool(hold), False, False, group
         self.adapter: Optional[int] = None   # the adapter id the request decodes under (a pool with lora_slots)
+        self.drafts = np.zeros((0, 8), dtype=np.int64)
 
 
 class DecodePool:
@@ -194,9 +253,24 @@ class DecodePool:
 
     def __init__(self, model, rows: int, capacity: int, generator=None, seeded: bool = False, prefix_slots: int = 0,
                  prefix_capacity: int = 0, kv_dtype: Optional[str] = None, logprobs: bool = False, lora_slots: int = 0,
-                 lora_rank: int = 64):
+                 lora_rank: int = 64, lookahead: Optional[int] = None):
         if int(rows) != rows or rows < 1 or int(capacity) != capacity or capacity < 2:
             raise ValueError(f"decode_pool: {rows} rows of capacity {capacity}")
+        if lookahead is not None:
+            if isinstance(lookahead, bool) or not isinstance(lookahead, (int, np.integer)) or lookahead < 1:
+                raise ValueError(f"decode_pool: lookahead={lookahead!r} -- an integer k >= 1, the draft rows of every request")
+            if not seeded:
+                raise ValueError("decode_pool: lookahead needs seeded=True -- exact verification rests on the seeded sampler, whose "
+                                 "draws depend on the request's seed and the event's index, not on the row or the step")
+            if prefix_slots or prefix_capacity or kv_dtype is not None or lora_slots:
+                raise ValueError("decode_pool: lookahead is not available together with prefix_slots, kv_dtype or lora_slots")
+            if rows * (int(lookahead) + 1) > 256:
+                raise ValueError(f"decode_pool: {rows} requests with lookahead={lookahead} need {rows * (int(lookahead) + 1)} session "
+                                 f"rows (rows x (lookahead + 1)); at most 256")
+        self.lookahead = int(lookahead) if lookahead is not None else 0
+        self.proposer = propose_ngram   # (a lookahead pool) history [N, 8], k -> up to k guessed next events; replaceable
+        self.steps = 0                  # step() calls that launched something (tools and tests count them)
+        self.drafted = self.accepted = 0   # (a lookahead pool) guesses that a draft row consumed, and those that proved right
         if kv_dtype is not None:
             if kv_dtype != "fp8":
                 raise ValueError(f"decode_pool: kv_dtype={kv_dtype!r} -- None (the cache in the model's dtype) or \"fp8\"")
@@ -464,8 +538,10 @@ class DecodePool:
                 slots["logprobs"] = True
             if self.lora_slots:  # (likewise)
                 slots.update(lora_slots=self.lora_slots, lora_rank=self.lora_rank)
-            ses = self.model._checkout_session(self.rows, self.capacity, 1.0, 0.98, 1, ragged=True, row_params=True,
-                                                seeded=self.seeded, **slots)
+            if self.lookahead:  # (likewise) a group of lookahead + 1 session rows per request
+                slots["lookahead"] = self.lookahead
+            ses = self.model._checkout_session(self.rows * (self.lookahead + 1), self.capacity, 1.0, 0.98, 1, ragged=True,
+                                                row_params=True, seeded=self.seeded, **slots)
             ses.reset()                      # every row free: pos = pos_limit = 0
             ses.begin(self.generator)
             self.ses = ses
@@ -556,6 +632,9 @@ class DecodePool:
                                    f"at the head of the queue cannot be admitted: {len(self.free)} rows are free{slots}, "
                                    f"{len(self.held_rows)} held -- drop() a held request")
             ses = self.ses
+            self.steps += 1
+            if self.lookahead:
+                return self._step_lookahead(eos)
             live = [row in self.occupied for row in range(self.rows)]
             running = [self.requests[rid] for rid in self.occupied.values()]
             # (a request that is to be held needs the net step over its LAST event too: its K/V row max_len - 1 and the hidden row
@@ -592,4 +671,92 @@ class DecodePool:
                 for row in finished:
                     self.requests[self.occupied.pop(row)].row = None
                 self.free = sorted(self.free + finished)
+        return out
+
+    # ---- lookahead (the module docstring, "LOOKAHEAD") --------------------------------------------------------------------------
+    @staticmethod
+    def accept(samples: np.ndarray, drafts: np.ndarray, t: int, max_len: int, eos_id: int) -> int:
+        """the acceptance rule -> the number of TRUE events at the head of ``samples`` (>= 1).  samples [k + 1, 8]: row j of the
+        group sampled samples[j] for event index t + j; drafts [<= k, 8]: drafts[i - 1] is what row i consumed as event t + i - 1 in
+        the previous net step.  samples[0] is true; samples[i] is true iff samples[i - 1] is and drafts[i - 1] equals it in all 8
+        tokens.  The run ends behind an EOS and behind the event that brings the request to ``max_len`` events."""
+        n = 1
+        while not (samples[n - 1][0] == eos_id or t + n >= max_len or n > len(drafts) or n >= len(samples)
+                   or not np.array_equal(drafts[n - 1], samples[n - 1])):
+            n += 1
+        return n
+
+    def _drafts(self, r: _Request, history: np.ndarray) -> np.ndarray:
+        """the proposer's guess for the events behind ``history`` (request r's prompt + result), checked, and cut to the rows that can
+        sample an event below ``max_len`` (draft row j samples index len(history) + j)"""
+        k = self.lookahead
+        T, V = self.model.tokenizer.max_token_seq, self.model.tokenizer.vocab_size
+        room = min(k, r.max_len - 1 - len(history))
+        if room < 1:
+            return np.zeros((0, T), dtype=np.int64)
+        d = np.asarray(self.proposer(history, k))
+        if d.size == 0:
+            return np.zeros((0, T), dtype=np.int64)
+        if d.ndim != 2 or d.shape[1] != T or len(d) > k or d.dtype.kind not in "iu" or d.min() < 0 or d.max() >= V:
+            raise ValueError(f"DecodePool.step: the proposer returned {d.dtype} {tuple(d.shape)}: at most {k} events of {T} token ids "
+                             f"in [0, {V}) are a guess")
+        return d[:room].astype(np.int64)
+
+    def _step_lookahead(self, eos: int) -> List[Tuple[int, np.ndarray, bool]]:
+        """steps 1 to 4 of the module docstring, behind the admissions; ``row`` of a request is its GROUP here.  The host part is
+        planned first and committed afterwards, so that a proposer that raises, or returns what is no guess, leaves every request as
+        it was: the next ``step()`` samples the same events again (the seeded sampler's draws are a function of the state)."""
+        ses, gw = self.ses, self.lookahead + 1
+        live = [False] * (self.rows * gw)   # (the break rule of the step-by-step form: every row whose sample may be accepted)
+        for g, rid in self.occupied.items():
+            for j in range(len(self.requests[rid].drafts) + 1):
+                live[g * gw + j] = True
+        event, _ = ses.sample_event(then_net=False, live=live)
+        if self.want_logprobs:
+            logp, arity = np.cumsum(ses.last_logp, axis=1, dtype=np.float32), self.model._grammar()[3]
+        plan = []   # (group, request, true events, their ll, eos, done, the drafts for the next net step)
+        for g, rid in sorted(self.occupied.items(), key=lambda kv: kv[1]):
+            r = self.requests[rid]
+            t = len(r.prompt) + len(r.events)
+            samples = event[g * gw:(g + 1) * gw]
+            n = self.accept(samples, r.drafts, t, r.max_len, eos)
+            evs = [samples[i].copy() for i in range(n)]
+            is_eos = bool(evs[-1][0] == eos)
+            # an accepted event's ll comes from the row that sampled it
+            ll = [logp[g * gw + i, 0 if evs[i][0] == eos else arity[int(evs[i][0])]] for i in range(n)] if self.want_logprobs else []
+            done = is_eos or t + n >= r.max_len
+            drafts = r.drafts[:0] if done else self._drafts(r, np.concatenate([r.prompt] + [e[None] for e in r.events + evs], axis=0))
+            plan.append((g, rid, r, evs, ll, is_eos, done, drafts))
+        out, finished, keep = [], [], []
+        rows, inputs, poss, caches = [], [], [], []
+        for g, rid, r, evs, ll, is_eos, done, drafts in plan:
+            r.events += evs
+            r.logp += ll
+            self.drafted, self.accepted = self.drafted + len(r.drafts), self.accepted + len(evs) - 1
+            r.eos, r.done, r.drafts = is_eos, done, drafts
+            out += [(rid, ev, done and i == len(evs) - 1) for i, ev in enumerate(evs)]
+            if done and not (r.hold and not is_eos):
+                finished.append(g)
+                continue
+            if done:  # to be held: the net step over its final event, the draft rows inactive
+                keep.append(g)
+            # the group's inputs for the net step: the leader consumes the last true event, draft row j the j-th guess behind it
+            t, m = len(r.prompt) + len(r.events), len(drafts)
+            rows += [g * gw + j for j in range(gw)]
+            inputs += [evs[-1]] + list(drafts) + [evs[-1]] * (gw - 1 - m)
+            poss += [t - 1 + j for j in range(m + 1)] + [0] * (gw - 1 - m)
+            caches += [g] * (m + 1) + [-1] * (gw - 1 - m)
+        if rows:  # a request continues, or is to be held
+            ses.set_inputs(rows, np.stack(inputs), poss, caches)
+            ses.net_step()
+        if keep:  # (behind the net step over their last event: the leaders stay parked at max_len, nothing is released)
+            ses.hold(keep)
+            for g in keep:
+                rid = self.held_rows[g] = self.occupied.pop(g)
+                self.requests[rid].held = True
+        if finished:
+            ses.release(finished)
+            for g in finished:
+                self.requests[self.occupied.pop(g)].row = None
+            self.free = sorted(self.free + finished)
         return out
